@@ -2,6 +2,7 @@
 """Benchmark of the NeRFace ray-marching hot path on MI355X.
 
     python bench.py --gpus N --steps K --warmup W          (N>1: launched by torch.distributed.run)
+    python bench.py ... --dump-outputs DIR                 (also: the last timed step's outputs as DIR/<name>.npy, seeded inputs)
 
 One *step* = one full 512x512 frame through the product path exactly as eval_transformed_rays.py drives it:
 `get_ray_bundle` + `run_one_iter_of_nerf(mode="validation")` with the shipped validation settings (64 coarse + 128 fine
@@ -179,6 +180,23 @@ def train_roofline(args, model, dev, n_rays):
                     "eval line's PMC passes, tools/pmc_train_launch.py)"}
 
 
+DUMP_LIMIT = 64 << 20           # bytes: --dump-outputs writes at most this much
+RENDER_OUTPUTS = ("rgb_coarse", "disp_coarse", "acc_coarse", "rgb_fine", "disp_fine", "acc_fine", "weights_fine_last")
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: {name: tensor} -> dirname/<name>.npy, float64 kept, everything else as float32.  The inputs of the timed
+    path are seeded, so two builds run with the same arguments can be compared file by file."""
+    arrays = {k: v.detach().cpu().numpy() for k, v in arrays.items() if v is not None}
+    arrays = {k: a if a.dtype == np.float64 else a.astype(np.float32) for k, a in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT:
+        raise SystemExit(f"bench.py --dump-outputs: {total} bytes exceed the {DUMP_LIMIT}-byte limit")
+    os.makedirs(dirname, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(dirname, k + ".npy"), a)
+
+
 def bench_train(args, nerf, model_c, model_f, dev, rank, world, dist, emit=True):
     """configs[2] / configs[4]: the trainer's iteration (TR:289-400) on synthetic data -- full-frame ray bundle, 2048 random
     rays, run_one_iter_of_nerf(mode='train') with the shipped training settings (64+64, chunksize 2048, perturb, noise
@@ -227,17 +245,17 @@ def bench_train(args, nerf, model_c, model_f, dev, rank, world, dist, emit=True)
         reducer.reduce()
         optim.step()
         optim.zero_grad()
-        return loss
+        return loss, out
 
     for i in range(args.warmup):
-        loss = step(i)
+        loss, out = step(i)
     torch.cuda.synchronize()
     if dist is not None:
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for i in range(args.warmup, n_it):
-        loss = step(i)
+        loss, out = step(i)
     torch.cuda.synchronize()
     if dist is not None:
         dist.barrier()
@@ -248,6 +266,11 @@ def bench_train(args, nerf, model_c, model_f, dev, rank, world, dist, emit=True)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     assert bool(torch.isfinite(loss))
+    if args.dump_outputs and emit and rank == 0:
+        # the last step's loss and renders, and the parameters its Adam update left
+        dump_outputs(args.dump_outputs, {"loss": loss, **dict(zip(RENDER_OUTPUTS, out)), "latent_codes": latent_codes,
+                                         **{"coarse." + k: v for k, v in model_c.named_parameters()},
+                                         **{"fine." + k: v for k, v in model_f.named_parameters()}})
     roofline = train_roofline(args, model_f, dev, n_rays) if rank == 0 else None
     allreduce = reducer.stats()          # ranks the communicator saw, bytes per step, median HIP-event time of the collective
     result = None
@@ -369,6 +392,24 @@ def self_launch(n):
     return subprocess.call(cmd)
 
 
+def ensure_library():
+    """Build libnerface_hip.so when it is stale.  Ranks that find it stale take a file lock beside it; the first builds, the
+    others then find it fresh.  A fresh library (what __graft_entry__.build() leaves) is used as it is and nothing is written,
+    so the benchmark runs from a checkout it cannot write to."""
+    import fcntl
+    import __graft_entry__ as G
+    B = G._load_build()
+    if not B._stale():
+        return
+    os.makedirs(B.OUT_DIR, exist_ok=True)
+    with open(os.path.join(B.OUT_DIR, ".build.lock"), "w") as lock:
+        fcntl.flock(lock, fcntl.LOCK_EX)
+        try:
+            B.build(force=False, verbose=False)
+        finally:
+            fcntl.flock(lock, fcntl.LOCK_UN)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -390,6 +431,8 @@ def main():
     ap.add_argument("--cpu-rays", type=int, default=12288)
     ap.add_argument("--train-steps", type=int, default=40, help="iterations of the `train` object of the eval line")
     ap.add_argument("--launcher-frames", type=int, default=32, help="frames of the launch/eval_sharded.py throughput leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the headline's last timed step returned (rank 0) as DIR/<name>.npy")
     args = ap.parse_args()
 
     backend = os.environ.get("NERFACE_DIST_BACKEND", "nccl")           # "gloo": several ranks on one GPU (tests of the N > 1 path)
@@ -418,17 +461,8 @@ def main():
     dist = None
     force_pg = os.environ.get("NERFACE_DIST_FORCE", "0") not in ("", "0")   # world 1 under torch.distributed.run: run the collectives anyway (RCCL smoke)
     # the library BEFORE the process group: a cold box may have to compile it (minutes), and a rank that compiles while the others
-    # sit in RCCL's init / first barrier can run them into the collective timeout.  Every rank takes a file lock; the first builds
-    # (a no-op when the pushed .so is fresh), the others find it fresh.
-    import fcntl
-    import __graft_entry__ as G
-    os.makedirs(os.path.join(PKG, "lib"), exist_ok=True)
-    with open(os.path.join(PKG, "lib", ".build.lock"), "w") as lock:
-        fcntl.flock(lock, fcntl.LOCK_EX)
-        try:
-            G._load_build().build(force=False, verbose=False)
-        finally:
-            fcntl.flock(lock, fcntl.LOCK_UN)
+    # sit in RCCL's init / first barrier can run them into the collective timeout
+    ensure_library()
     if world > 1 or force_pg:
         import datetime
         import torch.distributed as dist
@@ -496,9 +530,12 @@ def main():
         else:
             per_rank = [1e3 * own / max(args.steps, 1)]
         assert out[3].shape == (H, W, 3) and bool(torch.isfinite(out[3]).all())
-        return dt, per_rank
+        return dt, per_rank, out
 
-    dt, per_rank_ms = timed_frames()
+    dt, per_rank_ms, out = timed_frames()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, dict(zip(RENDER_OUTPUTS, out)))
+    del out
     rays_total = world * args.steps * H * W
     # what each arithmetic is, and which targets it keeps north_star's 1e-4 dB gate against (profiles/r06_gate_sensitivity.md, nerf.gate.EXPECTED_PASS)
     dtype_of = {"f32": "f32",
@@ -523,7 +560,7 @@ def main():
     if not args.no_extras:
         for other in others:
             nerf.set_mlp_precision(other)
-            dt_o, _ = timed_frames()
+            dt_o, _, _ = timed_frames()
             line[key_of[other]] = {
                 "value": rays_total / dt_o, "unit": "rays/s", "ms_per_step": 1e3 * dt_o / max(args.steps, 1), "steps": args.steps,
                 "warmup": args.warmup, "dtype": dtype_of[other],

@@ -1,4 +1,4 @@
-"""Generate tests/golden/*.npz by running the UNMODIFIED reference on CPU.  TEST INFRASTRUCTURE ONLY.
+"""Generate tests/golden/*.npz (and dropin_reference.json) by running the UNMODIFIED reference on CPU.  TEST INFRASTRUCTURE ONLY.
 
 Run inside the build container (where /root/reference exists):   python -m oracle.make_golden
 The fixtures hold reference OUTPUTS for the seeded synthetic cases of oracle/cases.py; inputs and
@@ -10,8 +10,14 @@ import os
 import sys
 import types
 
-import numpy as np
-import torch
+# `mkl_compatible NAME...`: those case fixtures again, computed on MKL's COMPATIBLE code branch, which gives the same results on
+# every x86 CPU; for the cases whose x1000 density head turns a host-BLAS ulp into more than the golden tolerance.  MKL reads
+# the setting when it initialises, so it is set before torch is imported.
+if sys.argv[1:2] == ["mkl_compatible"]:
+    os.environ["MKL_CBWR"] = "COMPATIBLE"
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from oracle import cases as C                      # noqa: E402
@@ -355,6 +361,97 @@ def make_pe_pdf(ref):
     print("pe_pdf fixture written (oracle == reference samples, bit exact)")
 
 
+# ---- drop-in conformance (tests/test_dropin_conformance.py): what the reference's callers use, as data ----------------------------
+DROPIN_SCRIPTS = ("train_transformed_rays.py", "eval_transformed_rays.py")
+DROPIN_FUNCTIONS = ("run_one_iter_of_nerf", "get_ray_bundle", "get_embedding_function", "positional_encoding", "sample_pdf_2",
+                    "volume_render_radiance_field", "predict_and_render_radiance", "run_network", "load_flame_data", "img2mse",
+                    "mse2psnr", "meshgrid_xy", "cumprod_exclusive", "get_minibatches")
+# model families with a fused HIP path (the paper model, 88 config entries; §8(f2): the learnable-code model, 6)
+DROPIN_MODELS = ("ConditionalBlendshapePaperNeRFModel", "ConditionalBlendshapeLearnableCodeNeRFModel")
+DROPIN_MODEL_KW = dict(num_encoding_fn_xyz=10, num_encoding_fn_dir=4, include_input_xyz=True, include_input_dir=False, use_viewdirs=True,
+                       num_layers=4, hidden_size=256, include_expression=True)
+
+
+def nerf_imports(tree):
+    """{local name: [module, attribute]} for every `from nerf[.x] import a [as b]`."""
+    import ast
+    out = {}
+    for node in ast.walk(tree):
+        if isinstance(node, ast.ImportFrom) and node.module and (node.module == "nerf" or node.module.startswith("nerf.")):
+            for a in node.names:
+                out[a.asname or a.name] = [node.module, a.name]
+    return out
+
+
+def nerf_calls(tree, names):
+    """[callee, n_positional, keyword names, line] for calls of imported nerf names, and ["<model>", ...] for
+    getattr(models, ...)(...) / ["<model>:X", ...] for models.X(...) constructions."""
+    import ast
+    found = []
+    for node in ast.walk(tree):
+        if not isinstance(node, ast.Call):
+            continue
+        if any(isinstance(a, ast.Starred) for a in node.args) or any(k.arg is None for k in node.keywords):
+            continue
+        kws = [k.arg for k in node.keywords]
+        f = node.func
+        if isinstance(f, ast.Name) and f.id in names:
+            found.append([f.id, len(node.args), kws, node.lineno])
+        elif (isinstance(f, ast.Call) and isinstance(f.func, ast.Name) and f.func.id == "getattr" and f.args
+              and isinstance(f.args[0], ast.Name) and f.args[0].id == "models"):
+            found.append(["<model>", len(node.args), kws, node.lineno])
+        elif isinstance(f, ast.Attribute) and isinstance(f.value, ast.Name) and f.value.id == "models":
+            found.append(["<model>:" + f.attr, len(node.args), kws, node.lineno])
+    return found
+
+
+def dropin_record(ref):
+    """Read out of the unmodified reference: per caller script (TR, EV; parsed with `ast`) every name it imports from `nerf` and
+    every call of one; the parameter names and defaults of the public functions (a parameter without a default is [name]); the
+    model `type:` counts of the shipped config/*.yml; the state_dict keys and shapes of the in-scope model families."""
+    import ast
+    import glob
+    import inspect
+    import json
+    import re
+    rec = {"scripts": {}, "signatures": {}, "config_model_types": {}, "state_dicts": {}}
+    for script in DROPIN_SCRIPTS:
+        path = os.path.join(RI.REF_ROOT, script)
+        tree = ast.parse(open(path).read(), filename=path)
+        names = nerf_imports(tree)
+        rec["scripts"][script] = {"imports": names, "calls": nerf_calls(tree, set(names))}
+    for fn in DROPIN_FUNCTIONS:
+        rec["signatures"][fn] = [[p.name] if p.default is inspect.Parameter.empty else [p.name, p.default]
+                                 for p in inspect.signature(getattr(ref, fn)).parameters.values()]
+    types = rec["config_model_types"]
+    for path in sorted(glob.glob(os.path.join(RI.REF_ROOT, "config", "**", "*.yml"), recursive=True)):
+        for m in re.finditer(r"^\s*type:\s*([A-Za-z_0-9]+)\s*$", open(path).read(), re.M):
+            if m.group(1).endswith("Model"):
+                types[m.group(1)] = types.get(m.group(1), 0) + 1
+    for t in DROPIN_MODELS:
+        rec["state_dicts"][t] = [[k, list(v.shape)] for k, v in getattr(ref.models, t)(**DROPIN_MODEL_KW).state_dict().items()]
+    return json.loads(json.dumps(rec))                                 # the form the fixture is read back in (tuples -> lists)
+
+
+def make_dropin(ref):
+    import json
+    with open(os.path.join(OUT, "dropin_reference.json"), "w") as f:
+        json.dump(dropin_record(ref), f, indent=1, sort_keys=True)
+        f.write("\n")
+
+
+def make_flex_mlp(ref):
+    """FlexibleNeRFModel.forward (M:396-422, use_viewdirs=False) on seeded encoded points for 2, 4 and 5 layers."""
+    x = torch.randn((257, 63), generator=torch.Generator().manual_seed(5))
+    out = {}
+    for L in (2, 4, 5):
+        m = ref.models.FlexibleNeRFModel(num_layers=L, hidden_size=128, num_encoding_fn_xyz=10, include_input_xyz=True, use_viewdirs=False)
+        m.load_state_dict(O.flex_init_params(17 + L, L))
+        with torch.no_grad():
+            out[f"out_L{L}"] = m(x).numpy()
+    np.savez_compressed(os.path.join(OUT, "flex_mlp_257.npz"), **out)
+
+
 def main():
     os.makedirs(OUT, exist_ok=True)
     ref = RI.import_reference()
@@ -383,8 +480,16 @@ def main():
     if len(sys.argv) > 1 and sys.argv[1] == "eval_as_shipped":
         make_eval_as_shipped()
         return
+    if len(sys.argv) > 1 and sys.argv[1] == "dropin":
+        make_dropin(ref)
+        return
+    if len(sys.argv) > 1 and sys.argv[1] == "flex_mlp":
+        make_flex_mlp(ref)
+        return
     names7 = ["rgb_c", "disp_c", "acc_c", "rgb_f", "disp_f", "acc_f", "w_last"]
     only = sys.argv[2:] if len(sys.argv) > 2 and sys.argv[1] == "cases" else None     # `cases NAME...`: only these 7-tuple fixtures
+    suffix = "_mkl_compatible" if sys.argv[1:2] == ["mkl_compatible"] else ""
+    only = sys.argv[2:] if suffix else only
     for name in (only or C.CASES):
         c = C.build_case(name)
         out_ref, _ = run_reference(ref, c)
@@ -398,7 +503,7 @@ def main():
             exact = torch.equal(a, b)
             print(f"[{name}] {n}: exact={exact} max|d|={float((a - b).abs().max()):.3e}")
             blob[n] = a.numpy()
-        np.savez_compressed(os.path.join(OUT, f"{name}.npz"), **blob)
+        np.savez_compressed(os.path.join(OUT, f"{name}{suffix}.npz"), **blob)
     if only:
         return
 
@@ -479,6 +584,8 @@ def main():
     make_load_flame()
     make_tiny_grads(ref)
     make_flex_tiny(ref)
+    make_flex_mlp(ref)
+    make_dropin(ref)
 
     # tiny_nerf (BASELINE config 1): 64x64, 32 samples, 3-layer 128-wide MLP, coarse only
     TN = RI.import_reference_tiny()

@@ -1,60 +1,30 @@
-"""Drop-in conformance GENERATED from the reference's two caller scripts (CPU; skipped where /root/reference is absent).
+"""Drop-in conformance GENERATED from the reference's two caller scripts (CPU).
 
-train_transformed_rays.py (TR) and eval_transformed_rays.py (EV) are parsed with `ast`; every name they import from `nerf`
-(TR:17-21, EV:30-39), every call they make to one of those names -- positional arity and keyword names --, every
-`getattr(models, cfg.models.<net>.type)(...)` construction (TR:100-124, EV:274-299) and every model `type:` the shipped
-YAML configs name are collected, and the product package must accept each of them (inspect.signature(...).bind).  Nothing
-here is typed in by hand: if a script passes a keyword the product does not take, this test names the call site."""
-import ast
-import glob
+train_transformed_rays.py (TR) and eval_transformed_rays.py (EV) are parsed with `ast` by oracle/make_golden.py (`dropin`), which
+stores in tests/golden/dropin_reference.json every name they import from `nerf` (TR:17-21, EV:30-39), every call they make to one
+of those names -- positional arity and keyword names --, every `getattr(models, cfg.models.<net>.type)(...)` construction
+(TR:100-124, EV:274-299), the signatures of the public functions, every model `type:` the shipped YAML configs name and the
+state_dict schema of the in-scope families.  The product package must accept each of them (inspect.signature(...).bind).
+Nothing here is typed in by hand: if a script passes a keyword the product does not take, this test names the call site.  Where
+the reference tree is present, the stored record is checked against a fresh extraction."""
 import inspect
+import json
 import os
-import re
 
 import pytest
+import torch
 
+from oracle import make_golden as MG
 from oracle import ref_import as RI
 
-pytestmark = pytest.mark.skipif(not RI.reference_available(), reason="/root/reference only exists in the build container")
-SCRIPTS = ("train_transformed_rays.py", "eval_transformed_rays.py")
-# model families with a fused HIP path (the paper model, 88 config entries; §8(f2): the learnable-code model, 6)
-IN_SCOPE_MODELS = ("ConditionalBlendshapePaperNeRFModel", "ConditionalBlendshapeLearnableCodeNeRFModel")
+SCRIPTS = MG.DROPIN_SCRIPTS
+IN_SCOPE_MODELS = MG.DROPIN_MODELS
+RECORD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "dropin_reference.json")
 
 
-def _parse(script):
-    path = os.path.join(RI.REF_ROOT, script)
-    return ast.parse(open(path).read(), filename=path)
-
-
-def _nerf_imports(tree):
-    """{local name: (module, attribute)} for every `from nerf[.x] import a [as b]`."""
-    out = {}
-    for node in ast.walk(tree):
-        if isinstance(node, ast.ImportFrom) and node.module and (node.module == "nerf" or node.module.startswith("nerf.")):
-            for a in node.names:
-                out[a.asname or a.name] = (node.module, a.name)
-    return out
-
-
-def _calls(tree, names):
-    """(callee, n_positional, keyword names, line) for calls of imported nerf names, and ("<model>", ...) for
-    getattr(models, ...)(...) / models.X(...) constructions."""
-    found = []
-    for node in ast.walk(tree):
-        if not isinstance(node, ast.Call):
-            continue
-        if any(isinstance(a, ast.Starred) for a in node.args) or any(k.arg is None for k in node.keywords):
-            continue
-        kws = [k.arg for k in node.keywords]
-        f = node.func
-        if isinstance(f, ast.Name) and f.id in names:
-            found.append((f.id, len(node.args), kws, node.lineno))
-        elif (isinstance(f, ast.Call) and isinstance(f.func, ast.Name) and f.func.id == "getattr" and f.args
-              and isinstance(f.args[0], ast.Name) and f.args[0].id == "models"):
-            found.append(("<model>", len(node.args), kws, node.lineno))
-        elif isinstance(f, ast.Attribute) and isinstance(f.value, ast.Name) and f.value.id == "models":
-            found.append(("<model>:" + f.attr, len(node.args), kws, node.lineno))
-    return found
+def _record():
+    with open(RECORD) as f:
+        return json.load(f)
 
 
 def _product():
@@ -66,7 +36,7 @@ def _product():
 def test_every_imported_name_exists(script):
     import importlib
     nerf = _product()
-    names = _nerf_imports(_parse(script))
+    names = _record()["scripts"][script]["imports"]
     assert names, "no nerf imports found: the parser is looking at the wrong file"
     for local, (module, attr) in names.items():
         mod = nerf if module == "nerf" else importlib.import_module(module)      # e.g. `from nerf.load_flame import ...` (TR:17)
@@ -77,9 +47,8 @@ def test_every_imported_name_exists(script):
 @pytest.mark.parametrize("script", SCRIPTS)
 def test_every_call_site_binds(script):
     nerf = _product()
-    tree = _parse(script)
-    names = _nerf_imports(tree)
-    calls = _calls(tree, set(names))
+    rec = _record()["scripts"][script]
+    names, calls = rec["imports"], rec["calls"]
     seen = {c[0] for c in calls}
     assert {"run_one_iter_of_nerf", "get_ray_bundle", "get_embedding_function", "<model>"} <= seen, seen
     for callee, n_pos, kws, line in calls:
@@ -103,39 +72,38 @@ def test_every_call_site_binds(script):
 
 
 def test_run_one_iter_signature_is_the_references():
-    """Same parameter names, order and defaults as T:165-181 (taken from the reference's own function object)."""
-    ref = RI.import_reference()
+    """Same parameter names, order and defaults as T:165-181 (taken from the reference's own function objects)."""
     nerf = _product()
-    for fn in ("run_one_iter_of_nerf", "get_ray_bundle", "get_embedding_function", "positional_encoding", "sample_pdf_2",
-               "volume_render_radiance_field", "predict_and_render_radiance", "run_network", "load_flame_data", "img2mse", "mse2psnr",
-               "meshgrid_xy", "cumprod_exclusive", "get_minibatches"):
-        a, b = inspect.signature(getattr(ref, fn)), inspect.signature(getattr(nerf, fn))
-        pa = [(p.name, p.default) for p in a.parameters.values()]
+    empty = inspect.Parameter.empty
+    for fn, params in _record()["signatures"].items():
+        pa = [(p[0], p[1] if len(p) > 1 else empty) for p in params]
+        b = inspect.signature(getattr(nerf, fn))
         pb = [(p.name, p.default) for p in b.parameters.values()]
         assert [n for n, _ in pa] == [n for n, _ in pb][:len(pa)], (fn, pa, pb)
         for (n, da), (_, db) in zip(pa, pb):
-            assert (da is inspect.Parameter.empty) == (db is inspect.Parameter.empty) and (da is inspect.Parameter.empty or da == db), (fn, n, da, db)
-        assert all(d is not inspect.Parameter.empty for _, d in pb[len(pa):]), fn      # extensions must be optional
+            assert (da is empty) == (db is empty) and (da is empty or da == db), (fn, n, da, db)
+        assert all(d is not empty for _, d in pb[len(pa):]), fn      # extensions must be optional
 
 
 def test_model_types_of_the_shipped_configs():
     """Every `type:` under `models:` in the reference's config/*.yml: the two in-scope families must be constructible with the
     trainer's keyword set (and produce the reference's state_dict keys and shapes); the rest are listed as out of scope."""
-    ref = RI.import_reference()
+    rec = _record()
     nerf = _product()
-    types = {}
-    for path in glob.glob(os.path.join(RI.REF_ROOT, "config", "**", "*.yml"), recursive=True):
-        for m in re.finditer(r"^\s*type:\s*([A-Za-z_0-9]+)\s*$", open(path).read(), re.M):
-            if m.group(1).endswith("Model"):
-                types[m.group(1)] = types.get(m.group(1), 0) + 1
+    types = rec["config_model_types"]
     assert sum(types.values()) > 50 and set(IN_SCOPE_MODELS) <= set(types), types
     covered = sum(n for t, n in types.items() if t in IN_SCOPE_MODELS)
     print(f"model types in shipped configs: {types}; fused HIP path covers {covered} of {sum(types.values())} entries")
-    kw = dict(num_encoding_fn_xyz=10, num_encoding_fn_dir=4, include_input_xyz=True, include_input_dir=False, use_viewdirs=True,
-              num_layers=4, hidden_size=256, include_expression=True)
     for t in IN_SCOPE_MODELS:
-        a, b = getattr(ref.models, t)(**kw), getattr(nerf.models, t)(**kw)
-        sa, sb = a.state_dict(), b.state_dict()
+        sa = {k: torch.zeros(shape) for k, shape in rec["state_dicts"][t]}
+        b = getattr(nerf.models, t)(**MG.DROPIN_MODEL_KW)
+        sb = b.state_dict()
         assert list(sa) == list(sb) and all(sa[k].shape == sb[k].shape for k in sa), t
-        b.load_state_dict(sa)                                       # a reference checkpoint loads unchanged
+        b.load_state_dict(sa)                                       # a reference checkpoint's keys and shapes load unchanged
     assert covered >= 0.85 * sum(types.values())
+
+
+@pytest.mark.skipif(not RI.reference_available(), reason="the reference tree is not present here")
+def test_record_equals_live_reference():
+    """tests/golden/dropin_reference.json is what oracle/make_golden.py extracts from the reference tree today."""
+    assert MG.dropin_record(RI.import_reference()) == _record()

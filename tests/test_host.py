@@ -262,9 +262,44 @@ def test_bench_gpus_flag_is_honoured():
         B.subprocess.call = keep
     cmd = calls[0]
     assert cmd[1:4] == ["-m", "torch.distributed.run", "--nnodes=1"] and "--nproc-per-node=4" in cmd and "127.0.0.1" in cmd
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2"], env=dict(os.environ, WORLD_SIZE="1", RANK="0"),
+    # gloo: on a box with one GPU the nccl device-count check would answer first
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2"],
+                       env=dict(os.environ, WORLD_SIZE="1", RANK="0", NERFACE_DIST_BACKEND="gloo"),
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
     assert r.returncode != 0 and b"must agree" in r.stderr
+
+
+def test_bench_uses_a_fresh_library_without_writing(hip_lib, monkeypatch):
+    """bench.py runs from a checkout it cannot write to once __graft_entry__.build() has run: with the library fresh,
+    ensure_library() opens nothing for writing and creates no directory (no build lock)."""
+    import builtins
+    B = _load_bench()
+    keep = builtins.open
+
+    def read_only_open(file, mode="r", *a, **k):
+        assert not any(c in mode for c in "wax+"), (file, mode)
+        return keep(file, mode, *a, **k)
+
+    def no_makedirs(*a, **k):
+        raise AssertionError(("makedirs", a))
+
+    monkeypatch.setattr(builtins, "open", read_only_open)
+    monkeypatch.setattr(os, "makedirs", no_makedirs)
+    B.ensure_library()
+
+
+def test_bench_dump_outputs_writes_float_arrays_within_the_limit(tmp_path):
+    """bench.py --dump-outputs: one DIR/<name>.npy per returned array, float64 kept and every other dtype as float32, None
+    skipped; more than DUMP_LIMIT (64 MB) in all is refused before anything is written."""
+    B = _load_bench()
+    out = str(tmp_path / "d")
+    B.dump_outputs(out, {"rgb": torch.rand(4, 3).half(), "loss": torch.tensor(0.5, dtype=torch.float64), "w_last": None})
+    assert sorted(os.listdir(out)) == ["loss.npy", "rgb.npy"]
+    assert np.load(os.path.join(out, "rgb.npy")).dtype == np.float32 and np.load(os.path.join(out, "loss.npy")).dtype == np.float64
+    big = str(tmp_path / "big")
+    with pytest.raises(SystemExit):
+        B.dump_outputs(big, {"a": torch.zeros(B.DUMP_LIMIT // 4 + 1)})
+    assert not os.path.exists(big)
 
 
 def test_tiny_dw_job_table_selftest(hip_lib):

@@ -11,17 +11,34 @@ from oracle import cases as C
 from oracle import nerface_oracle as O
 from oracle import ref_import as RI
 
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
 NAMES7 = ["rgb_c", "disp_c", "acc_c", "rgb_f", "disp_f", "acc_f", "w_last"]
 
 
+def _oracle_on_mkl_compatible_branch(name, tmp_path):
+    """C.run_oracle of one case in a child process on MKL's COMPATIBLE code branch (the same results on every x86 CPU) with the
+    fixture recipe's 8 threads: MKL takes the branch when it initialises, so it cannot be switched inside this process."""
+    import subprocess
+    import sys
+    path = str(tmp_path / "out.npz")
+    code = ("import sys, numpy as np, torch; torch.set_num_threads(8); from oracle import cases as C; "
+            "out = C.run_oracle(C.build_case(sys.argv[1])); np.savez(sys.argv[2], *[np.zeros(0) if t is None else t.numpy() for t in out])")
+    subprocess.run([sys.executable, "-c", code, name, path], cwd=ROOT, env=dict(os.environ, MKL_CBWR="COMPATIBLE"), check=True, timeout=600)
+    blob = np.load(path)
+    return [None if blob[f"arr_{i}"].size == 0 else torch.from_numpy(blob[f"arr_{i}"]) for i in range(len(blob.files))]
+
+
 @pytest.mark.parametrize("name", list(C.CASES))
-def test_render_cases_match_golden(name):
+def test_render_cases_match_golden(name, tmp_path):
+    """Cases with a <name>_mkl_compatible.npz fixture (oracle/make_golden.py `mkl_compatible`): the x1000 density head turns a
+    host-BLAS ulp into more than the tolerance, so oracle and reference are compared on the one MKL branch every CPU shares."""
     c = C.build_case(name)
-    gold = np.load(os.path.join(GOLD, f"{name}.npz"))
+    compatible = os.path.join(GOLD, f"{name}_mkl_compatible.npz")
+    gold = np.load(compatible if os.path.exists(compatible) else os.path.join(GOLD, f"{name}.npz"))
     assert abs(float(gold["params_checksum"]) - (C.params_checksum(c["p_coarse"]) + C.params_checksum(c["p_fine"]))) < 1e-6, \
         "seeded weight generation drifted; regenerate the fixtures with oracle/make_golden.py"
-    out = C.run_oracle(c)
+    out = _oracle_on_mkl_compatible_branch(name, tmp_path) if os.path.exists(compatible) else C.run_oracle(c)
     for n, t in zip(NAMES7, out):
         if t is None:
             assert n not in gold.files
@@ -250,13 +267,19 @@ def test_flex_tiny_golden_and_gradient_fixture():
         assert float((v.grad - want).norm() / (want.norm() + 1e-30)) < 1e-5, k
 
 
-def test_flex_restatement_equals_live_reference_model():
-    """When the unmodified reference can be imported here: flex_mlp == FlexibleNeRFModel.forward on random encoded points, bit for bit."""
-    from oracle import ref_import as RI
-    if not RI.reference_importable():
-        pytest.skip("reference not importable here")
-    ref = RI.import_reference()
+def test_flex_restatement_equals_reference_model():
+    """flex_mlp against FlexibleNeRFModel.forward on random encoded points: the unmodified reference's outputs stored in
+    tests/golden/flex_mlp_257.npz and, when the reference can be imported here, the live model, bit for bit."""
+    g = np.load(os.path.join(GOLD, "flex_mlp_257.npz"))
     x = torch.randn((257, 63), generator=torch.Generator().manual_seed(5))
+    for L in (2, 4, 5):
+        p = O.flex_init_params(17 + L, L)
+        got = O.flex_mlp(p, x).numpy()
+        d = np.abs(got - g[f"out_L{L}"]).max()
+        assert np.array_equal(got, g[f"out_L{L}"]) or d < 1e-5, (L, d)         # another torch build may differ in BLAS blocking
+    if not RI.reference_importable():
+        return
+    ref = RI.import_reference()
     for L in (2, 4, 5):
         p = O.flex_init_params(17 + L, L)
         m = ref.models.FlexibleNeRFModel(num_layers=L, hidden_size=128, num_encoding_fn_xyz=10, include_input_xyz=True, use_viewdirs=False)
