@@ -177,7 +177,7 @@ class GradientAllReducer:
 
 def broadcast_parameters(params: Sequence[torch.Tensor], src: int = 0, group=None) -> None:
     """Identical initial state on every rank (model weights, latent table).  c10d collectives write into the storage
-    without touching the autograd version counter, and the packed-weight caches (ops.PaperWeights) are keyed on
+    without touching the autograd version counter, and the packed-weight caches (ops.MLPWeights) are keyed on
     (data_ptr, version): so the counters are bumped explicitly afterwards (one multi-tensor `x *= 1`), which invalidates
     every cached weight image that was packed before the broadcast."""
     _, world = world_info()

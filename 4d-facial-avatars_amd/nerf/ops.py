@@ -8,7 +8,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 import weakref
-from typing import Optional, Sequence
+from typing import NamedTuple, Optional, Sequence
 
 import numpy as np
 import torch
@@ -21,6 +21,8 @@ PAPER_KEYS = (
     + [f"layers_dir.{i}.{p}" for i in range(4) for p in ("weight", "bias")]
     + [f"fc_rgb.{p}" for p in ("weight", "bias")]
 )
+LCODE_KEYS = [f"{n}.{p}" for n in ("layer1", "layers_xyz.0", "layers_xyz.1", "layers_xyz.2", "layers_dir.0", "fc_alpha", "fc_rgb", "fc_feat")
+              for p in ("weight", "bias")]
 
 
 # Arithmetic of the MLP GEMMs: "f32" = exact-f32 MFMA (the library default and the arithmetic of the reference);
@@ -190,6 +192,31 @@ def posenc(x: torch.Tensor, n_freq: int, include_input: bool) -> torch.Tensor:
 
 
 # ---------------------------------------------------------------------------------------- K4
+class MLPFamily(NamedTuple):
+    """What tells the two fused NeRFace MLP families apart.  Every entry point of a family is `<prefix>_<name>`, with one C
+    signature per name for both families (include/nerface_hip.h)."""
+    prefix: str                 # "nf_paper" / "nf_lcode"
+    keys: tuple                 # parameter names, in the order of the ABI's parameter-pointer arrays and gradient images
+    hidden: tuple               # [lo, hi) of the hidden-activation sections of the exact-f32 `saved` buffer, in floats per point
+    none_grads: tuple           # gradient slots autograd leaves None
+    exact_dw: bool              # the split-bf16 backward takes (exact_dw, saved_f32)
+
+    def fn(self, name: str):
+        return getattr(H.lib(), f"{self.prefix}_{name}")
+
+    def call(self, name: str, *args) -> None:
+        """Launch `<prefix>_<name>(*args)`; a non-zero return code raises RuntimeError."""
+        H.check(self.fn(name)(*args), f"{self.prefix}_{name}")
+
+
+PAPER = MLPFamily("nf_paper", tuple(PAPER_KEYS),
+                  (64, 2240),           # S_H0 .. S_DIRF (csrc/nf_mlp_layout.h): h0 .. h5, fc_feat, layers_dir.0 .. 2
+                  (22, 23),             # layers_dir.3 exists in every checkpoint but is never used (Quirk Q3)
+                  True)
+LCODE = MLPFamily("nf_lcode", tuple(LCODE_KEYS),
+                  (64, 1472),           # S_L1 .. S_DIRF (csrc/nf_mlp_lcode_layout.h): layer1, layers_xyz.0 .. 2, fc_feat, layers_dir.0
+                  (), False)
+
 # Packed weight images are cached per (parameter storage, version counter, PACK EPOCH).  The version counter follows ordinary
 # in-place updates (optimizer.step() of the default / foreach optimizers, load_state_dict, copy_ under no_grad) -- but NOT every
 # writer bumps it: torch's FUSED optimizers (Adam(fused=True)), writes through `p.data` and c10d collectives leave it untouched.
@@ -206,25 +233,26 @@ def pack_epoch() -> int:
     return _PACK_EPOCH[0]
 
 
-class PaperWeights:
-    """Kernel-ready images of one ConditionalBlendshapePaperNeRFModel on one device, one per kind, each re-packed whenever a
-    parameter's version counter or the pack epoch moves (i.e. after optimizer.step() / load_state_dict() / a new frame or step):
+class MLPWeights:
+    """Kernel-ready images of one fused model of `family` on one device, one per kind, each re-packed whenever a parameter's
+    version counter or the pack epoch moves (i.e. after optimizer.step() / load_state_dict() / a new frame or step):
       f32 / f32_t      fragment-ordered f32 image for the forward / transposed image for the backward chain
       bf16 / bf16_t    (hi, lo) bf16 streams of the split-bf16 forward / chain
       f16 / f16_t      (hi, lo) fp16 streams + per-layer scales of the split-fp16 forward / chain."""
 
-    # kind -> (size function, pack function, element dtype)
+    # kind -> (size entry point, pack entry point, element dtype); names after the family prefix
     _KINDS = {
-        "f32": ("nf_paper_packed_floats", "nf_paper_pack", torch.float32),
-        "f32_t": ("nf_paper_packed_bwd_floats", "nf_paper_pack_bwd", torch.float32),
-        "bf16": ("nf_paper_packed_bf16_bytes", "nf_paper_pack_bf16", torch.uint8),
-        "bf16_t": ("nf_paper_packed_bwd_bf16_bytes", "nf_paper_pack_bwd_bf16", torch.uint8),
-        "f16": ("nf_paper_packed_f16_bytes", "nf_paper_pack_f16", torch.uint8),
-        "f16_t": ("nf_paper_packed_bwd_f16_bytes", "nf_paper_pack_bwd_f16", torch.uint8),
+        "f32": ("packed_floats", "pack", torch.float32),
+        "f32_t": ("packed_bwd_floats", "pack_bwd", torch.float32),
+        "bf16": ("packed_bf16_bytes", "pack_bf16", torch.uint8),
+        "bf16_t": ("packed_bwd_bf16_bytes", "pack_bwd_bf16", torch.uint8),
+        "f16": ("packed_f16_bytes", "pack_f16", torch.uint8),
+        "f16_t": ("packed_bwd_f16_bytes", "pack_bwd_f16", torch.uint8),
     }
 
-    def __init__(self, params: Sequence[torch.Tensor]):
-        assert len(params) == H.NF_PAPER_NUM_PARAMS
+    def __init__(self, family: MLPFamily, params: Sequence[torch.Tensor]):
+        assert len(params) == len(family.keys)
+        self.family = family
         self._params = list(params)
         self._cache = {}                # kind -> (signature, buffer)
         self._f16_sticky = None         # range-guard flag of the split-fp16 forward carried across re-packs (0-d int32 on the device)
@@ -245,18 +273,17 @@ class PaperWeights:
         if hit is None or hit[0] != sig:
             size_fn, pack_fn, dtype = self._KINDS[kind]
             dev = H.require_device(*[p.detach() for p in self._params])
-            lib = H.lib()
-            buf = hit[1] if hit is not None and hit[1].device == dev else torch.empty(getattr(lib, size_fn)(), dtype=dtype, device=dev)
+            buf = hit[1] if hit is not None and hit[1].device == dev else torch.empty(self.family.fn(size_fn)(), dtype=dtype, device=dev)
             if kind == "f16" and hit is not None and hit[1] is buf:
                 # packing clears the stream's range-guard flag: carry it over first (one tiny device op, no host sync), so that a
                 # training run polled every print_every iterations still sees an overflow of any iteration in between
                 if self._f16_sticky is None or self._f16_sticky.device != dev:
                     self._f16_sticky = torch.zeros((), dtype=torch.int32, device=dev)
-                off = lib.nf_paper_f16_flag_offset()
+                off = self.family.fn("f16_flag_offset")()
                 self._f16_sticky.bitwise_or_(buf[off:off + 4].view(torch.int32)[0])
-            arr = (C.c_void_p * H.NF_PAPER_NUM_PARAMS)(*[int(p.data_ptr()) for p in self._params])
+            arr = (C.c_void_p * len(self._params))(*[int(p.data_ptr()) for p in self._params])
             with torch.cuda.device(dev):
-                H.check(getattr(lib, pack_fn)(arr, H.ptr(buf), H.stream_ptr(dev)), pack_fn)
+                self.family.call(pack_fn, arr, H.ptr(buf), H.stream_ptr(dev))
             self._cache[kind] = (sig, buf)
         return self._cache[kind][1]
 
@@ -285,65 +312,156 @@ class PaperWeights:
         hit = self._cache.get("f16")
         if hit is None:
             return None
-        off = H.lib().nf_paper_f16_flag_offset()
+        off = self.family.fn("f16_flag_offset")()
         flag = hit[1][off:off + 4].view(torch.int32)[0]
         return flag if self._f16_sticky is None else torch.bitwise_or(flag, self._f16_sticky)
 
 
-def paper_condition(packed: torch.Tensor, expr: torch.Tensor, latent: torch.Tensor, near: float, far: float) -> torch.Tensor:
-    expr, latent = _c(expr.detach()), _c(latent.detach())
-    dev = H.require_device(packed, expr, latent)
+def check_conditioning(expr: torch.Tensor, latent: torch.Tensor) -> None:
+    """The conditioning kernels read expr[0..75] and latent[0..31] unconditionally: refuse other sizes before any launch."""
     if expr.numel() != 76 or latent.numel() != 32:
         raise ValueError("expected a 76-d expression and a 32-d latent code")
-    lib = H.lib()
-    cond = torch.empty(lib.nf_paper_cond_floats(), dtype=torch.float32, device=dev)
+
+
+def mlp_condition(fam: MLPFamily, packed, expr, latent, near: float, far: float) -> torch.Tensor:
+    """The per-call bias table of `fam` for one expression, latent code and near / far."""
+    expr, latent = _c(expr.detach()), _c(latent.detach())
+    dev = H.require_device(packed, expr, latent)
+    check_conditioning(expr, latent)
+    cond = torch.empty(fam.fn("cond_floats")(), dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
-        H.check(lib.nf_paper_condition(H.ptr(packed), H.ptr(expr), H.ptr(latent), float(np.float32(near)),
-                                       float(np.float32(far)), H.ptr(cond), H.stream_ptr(dev)), "nf_paper_condition")
+        fam.call("condition", H.ptr(packed), H.ptr(expr), H.ptr(latent), float(np.float32(near)), float(np.float32(far)), H.ptr(cond),
+                 H.stream_ptr(dev))
     return cond
 
 
-def paper_mlp_fwd(packed, cond, ro, rd, z, rd_view=None) -> torch.Tensor:
-    dev = H.require_device(packed, cond, ro, rd, z, rd_view)
+_FWD_ENTRY = {"f32": "mlp_fwd", "bf16x3": "mlp_fwd_bf16", "f16x3": "mlp_fwd_f16", "f16x2": "mlp_fwd_f16x2"}
+
+
+def mlp_fwd(fam: MLPFamily, precision: str, packed, cond, ro, rd, z, rd_view=None) -> torch.Tensor:
+    """Inference forward of `fam` in arithmetic `precision` -> raw (n_rays, n_samples, 4).  `packed` is the image of that arithmetic:
+    MLPWeights.get() for "f32", get_bf16() for "bf16x3", get_f16() for "f16x3" and "f16x2" (one image serves both)."""
+    dev = H.require_device(packed if precision == "f32" else None, cond, ro, rd, z, rd_view)
     n_rays, n_samples = z.shape
     raw = torch.empty((n_rays, n_samples, 4), dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
-        H.check(H.lib().nf_paper_mlp_fwd(H.ptr(packed), H.ptr(cond), H.ptr(ro), H.ptr(rd), H.ptr(rd_view), H.ptr(z),
-                                         n_rays, n_samples, H.ptr(raw), H.stream_ptr(dev)), "nf_paper_mlp_fwd")
+        fam.call(_FWD_ENTRY[precision], H.ptr(packed), H.ptr(cond), H.ptr(ro), H.ptr(rd), H.ptr(rd_view), H.ptr(z), n_rays, n_samples,
+                 H.ptr(raw), H.stream_ptr(dev))
     return raw
+
+
+def mlp_fwd_train(fam: MLPFamily, packed, cond, ro, rd, z, rd_view=None, packed_b=None, packed_h=None):
+    """Training forward of `fam`: returns (raw, (saved,)) where `saved` holds every layer output for the backward.
+    packed_b (split-bf16 stream) or packed_h (split-fp16 stream) given -> the forward runs on that split kernel and `saved`
+    additionally carries its ReLU bit masks; the matching backward is mlp_bwd(..., split=True / "f16")."""
+    dev = H.require_device(packed, cond, ro, rd, z, rd_view)
+    n_rays, n_samples = z.shape
+    raw = torch.empty((n_rays, n_samples, 4), dtype=torch.float32, device=dev)
+    saved = torch.empty(fam.fn("saved_floats")(n_rays * n_samples), dtype=torch.float32, device=dev)
+    entry, image = (("mlp_fwd_train_f16", packed_h) if packed_h is not None else
+                    ("mlp_fwd_train_bf16", packed_b) if packed_b is not None else ("mlp_fwd_train", packed))
+    with torch.cuda.device(dev):
+        fam.call(entry, H.ptr(image), H.ptr(cond), H.ptr(ro), H.ptr(rd), H.ptr(rd_view), H.ptr(z), n_rays, n_samples, H.ptr(raw),
+                 H.ptr(saved), H.stream_ptr(dev))
+    return raw, (saved,)
+
+
+def mlp_bwd(fam: MLPFamily, weights: MLPWeights, packed, cond, z, d_raw, saved_t, split=False, exact_dw=False):
+    """d_raw (n_rays, n_samples, 4) -> ([parameter gradients in fam.keys order, None in fam.none_grads], d_latent (32)).
+    saved_t: the `saved` buffer of the matching training forward.
+    split=True runs the dX chain on the split-bf16 kernel (requires `saved` from the split-bf16 training forward) and, unless
+    exact_dw (paper family only), the dW GEMMs too; split="f16" runs both on the split-fp16 kernels."""
+    if exact_dw and not fam.exact_dw:
+        raise ValueError(f"exact_dw: the split-bf16 backward of {fam.prefix} has no exact-f32 weight-gradient form")
+    d_raw = _c(d_raw)
+    dev = H.require_device(packed, cond, saved_t, d_raw)
+    n_rays, n_samples = z.shape
+    with torch.cuda.device(dev):             # the slice plan behind the size depends on the CURRENT device's CU count (nf_mlp_dw.h): ask on `dev`
+        ws_floats = fam.fn("bwd_workspace_floats")(n_rays * n_samples)
+    ws = torch.empty(ws_floats, dtype=torch.float32, device=dev)
+    flat = torch.empty(fam.fn("grad_floats")(), dtype=torch.float32, device=dev)
+    args = (H.ptr(cond), H.ptr(saved_t), H.ptr(d_raw), n_rays, n_samples, H.ptr(ws), ws_floats, H.ptr(flat))
+    with torch.cuda.device(dev):
+        if split == "f16":
+            fam.call("mlp_bwd_f16", H.ptr(packed), H.ptr(weights.get_f16_t()), *args, H.stream_ptr(dev))
+        elif split:
+            packed_bt, exact = weights.get_bf16_t(), ()
+            if fam.exact_dw:
+                saved_f32 = split_saved_to_f32(saved_t, n_rays * n_samples, False) if exact_dw else None   # the exact GEMMs read f32 rows
+                exact = (int(bool(exact_dw)), H.ptr(saved_f32))
+            fam.call("mlp_bwd_bf16", H.ptr(packed), H.ptr(packed_bt), *args, *exact, H.stream_ptr(dev))
+        else:
+            fam.call("mlp_bwd", H.ptr(packed), H.ptr(weights.get_t()), *args, H.stream_ptr(dev))
+    grads, off = [], 0
+    for i, p in enumerate(weights._params):
+        n = p.numel()
+        grads.append(None if i in fam.none_grads else flat[off:off + n].view(p.shape))
+        off += n
+    return grads, flat[off:off + 32]
+
+
+def mlp_forward_encoded(weights: MLPWeights, x, expr, latent) -> torch.Tensor:
+    """The model's forward on pre-encoded inputs x (N, 87) = [PE10(xyz) | PE4(dirs)] -> (N, 4) (inference)."""
+    x = _c(x.detach())
+    if x.dim() != 2 or x.shape[1] != 87:
+        raise ValueError("expected pre-encoded inputs of shape (N, 87)")
+    expr, latent = _c(expr.detach()).reshape(-1), _c(latent.detach()).reshape(-1)
+    check_conditioning(expr, latent)
+    packed = weights.get()
+    dev = H.require_device(packed, x, expr, latent)
+    fam = weights.family
+    cond = torch.empty(fam.fn("cond_floats")(), dtype=torch.float32, device=dev)
+    out = torch.empty((x.shape[0], 4), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        fam.call("forward_encoded", H.ptr(packed), H.ptr(x), H.ptr(expr), H.ptr(latent), x.shape[0], H.ptr(cond), H.ptr(out),
+                 H.stream_ptr(dev))
+    return out
+
+
+# the paper model's entry points under their historical names (bench.py, tools/ and the tests call them)
+def paper_condition(packed: torch.Tensor, expr: torch.Tensor, latent: torch.Tensor, near: float, far: float) -> torch.Tensor:
+    return mlp_condition(PAPER, packed, expr, latent, near, far)
+
+
+def paper_mlp_fwd(packed, cond, ro, rd, z, rd_view=None) -> torch.Tensor:
+    return mlp_fwd(PAPER, "f32", packed, cond, ro, rd, z, rd_view)
 
 
 def paper_mlp_fwd_bf16(packed_b, cond, ro, rd, z, rd_view=None) -> torch.Tensor:
     """Split-bf16 (3 x bf16 MFMA, f32 accumulate) forward; same outputs as paper_mlp_fwd to ~1e-5 relative."""
-    dev = H.require_device(cond, ro, rd, z, rd_view)
-    n_rays, n_samples = z.shape
-    raw = torch.empty((n_rays, n_samples, 4), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        H.check(H.lib().nf_paper_mlp_fwd_bf16(H.ptr(packed_b), H.ptr(cond), H.ptr(ro), H.ptr(rd), H.ptr(rd_view), H.ptr(z),
-                                              n_rays, n_samples, H.ptr(raw), H.stream_ptr(dev)), "nf_paper_mlp_fwd_bf16")
-    return raw
+    return mlp_fwd(PAPER, "bf16x3", packed_b, cond, ro, rd, z, rd_view)
 
 
 def paper_mlp_fwd_f16(packed_h, cond, ro, rd, z, rd_view=None) -> torch.Tensor:
     """Split-fp16 (3 x fp16 MFMA on scaled weights, f32 accumulate) forward; fp32-class accuracy (see csrc/nf_mlp_f16.hip)."""
-    dev = H.require_device(cond, ro, rd, z, rd_view)
-    n_rays, n_samples = z.shape
-    raw = torch.empty((n_rays, n_samples, 4), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        H.check(H.lib().nf_paper_mlp_fwd_f16(H.ptr(packed_h), H.ptr(cond), H.ptr(ro), H.ptr(rd), H.ptr(rd_view), H.ptr(z),
-                                             n_rays, n_samples, H.ptr(raw), H.stream_ptr(dev)), "nf_paper_mlp_fwd_f16")
-    return raw
+    return mlp_fwd(PAPER, "f16x3", packed_h, cond, ro, rd, z, rd_view)
 
 
 def paper_mlp_fwd_f16x2(packed_h, cond, ro, rd, z, rd_view=None) -> torch.Tensor:
     """"f16x2" forward: the split-fp16 kernel with two products per weight (csrc/nf_mlp_f16x2.hip) on the SAME packed image as f16x3."""
-    dev = H.require_device(cond, ro, rd, z, rd_view)
-    n_rays, n_samples = z.shape
-    raw = torch.empty((n_rays, n_samples, 4), dtype=torch.float32, device=dev)
+    return mlp_fwd(PAPER, "f16x2", packed_h, cond, ro, rd, z, rd_view)
+
+
+def paper_mlp_fwd_train(packed, cond, ro, rd, z, rd_view=None, packed_b=None, packed_h=None):
+    return mlp_fwd_train(PAPER, packed, cond, ro, rd, z, rd_view, packed_b=packed_b, packed_h=packed_h)
+
+
+def paper_mlp_bwd(model, packed, cond, z, d_raw, saved, split=False, exact_dw=False):
+    (saved_t,) = saved
+    return mlp_bwd(PAPER, model.hip_weights(), packed, cond, z, d_raw, saved_t, split=split, exact_dw=exact_dw)
+
+
+def split_saved_to_f32(saved_t: torch.Tensor, n_points: int, f16: bool, family: str = "paper") -> torch.Tensor:
+    """The activations a SPLIT training forward saved (fragment streams of (hi, lo) pairs, sections padded to 32 points) converted to
+    the exact-f32 training layout (sections [n_points][width] f32 rows at nfl::S_* x n_points): for tests and for the exact-f32
+    weight-gradient GEMMs on a split forward (paper_mlp_bwd(..., exact_dw=True))."""
+    fam = LCODE if family == "lcode" else PAPER
+    dev = H.require_device(saved_t)
+    out = torch.empty(fam.fn("saved_floats")(n_points), dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
-        H.check(H.lib().nf_paper_mlp_fwd_f16x2(H.ptr(packed_h), H.ptr(cond), H.ptr(ro), H.ptr(rd), H.ptr(rd_view), H.ptr(z),
-                                               n_rays, n_samples, H.ptr(raw), H.stream_ptr(dev)), "nf_paper_mlp_fwd_f16x2")
-    return raw
+        H.check(H.lib().nf_split_saved_to_f32(int(fam is LCODE), H.ptr(saved_t), n_points, int(bool(f16)), H.ptr(out), H.stream_ptr(dev)),
+                "nf_split_saved_to_f32")
+    return out
 
 
 def require_trainable_precision() -> None:
@@ -369,9 +487,9 @@ F16_PREFLIGHT_MARGIN = 4.0               # the probe refuses a model whose sampl
 
 
 def f16_preflight(model, ro, rd, z, rd_view, expr, latent, near, far, max_rays: int = 256, max_samples: int = 8) -> float:
-    """Range probe for the split-fp16 kernel: evaluate the EXACT-f32 training forward (which writes every layer's activations)
-    on a strided sample of the chunk's points and return the largest hidden |activation|.  ~2k points: microseconds of GPU
-    time and one host read-back; called once per frame and model by run_one_iter_of_nerf under "f16x3"."""
+    """Range probe for the split-fp16 kernel: evaluate the model family's EXACT-f32 training forward (which writes every layer's
+    activations) on a strided sample of the chunk's points and return the largest hidden |activation|.  ~2k points: microseconds
+    of GPU time and one host read-back."""
     n_rays, n_s = z.shape
     rs = max(1, n_rays // max_rays)
     ss = max(1, n_s // max_samples)
@@ -380,10 +498,33 @@ def f16_preflight(model, ro, rd, z, rd_view, expr, latent, near, far, max_rays: 
     rv_s = None if rd_view is None else rd_view[::rs].contiguous()
     hw = model.hip_weights()
     packed = hw.get()
-    cond = paper_condition(packed, expr, latent, near, far)
-    _, (saved,) = paper_mlp_fwd_train(packed, cond, ro_s, rd_s, z_s, rv_s)
+    cond = mlp_condition(hw.family, packed, expr, latent, near, far)
+    _, (saved,) = mlp_fwd_train(hw.family, packed, cond, ro_s, rd_s, z_s, rv_s)
+    lo, hi = hw.family.hidden
     n = z_s.numel()
-    return float(saved[64 * n:2240 * n].abs().max().item())          # sections S_H0 .. S_D2 (csrc/nf_mlp_layout.h): every hidden layer output
+    return float(saved[lo * n:hi * n].abs().max().item())
+
+
+def f16_guard(model, ro, rd, z, rd_view, expr, latent, near, far, training: bool) -> None:
+    """Refuse `model` before a split-fp16 launch when f16_preflight finds hidden activations within F16_PREFLIGHT_MARGIN of the fp16
+    range.  Inference probes once per (weights, conditioning), i.e. once per frame and model; in training the weights move every
+    step, so a model's first call and every f16_train_probe_every()-th after it are probed."""
+    state = model.__dict__
+    if training:
+        n_calls = state["_f16_train_calls"] = state.get("_f16_train_calls", 0) + 1
+        if not (_f16_train_probe_every[0] == 1 or n_calls % _f16_train_probe_every[0] == 1):
+            return
+    else:
+        key = (model.hip_weights()._signature()[1:], expr.data_ptr(), latent.data_ptr(), expr._version, latent._version)
+        if state.get("_f16_probe_key") == key:
+            return
+    amax = f16_preflight(model, ro, rd, z, rd_view, expr, latent, near, far)
+    if not amax * F16_PREFLIGHT_MARGIN < F16_ACT_LIMIT:
+        where, use = (", ", "train") if training else (" on a sample of this frame, ", "render")
+        raise RuntimeError(f'nerf.set_mlp_precision("{_mlp_precision}"): hidden activations of {type(model).__name__} reach {amax:.3g}{where}'
+                           f'within {F16_PREFLIGHT_MARGIN:g}x of the fp16 range limit ({F16_ACT_LIMIT:g}) -- {use} this model with "f32" or "bf16x3"')
+    if not training:
+        state["_f16_probe_key"] = key
 
 
 def check_f16_range(*models, sync_ranks: bool = False) -> None:
@@ -403,81 +544,6 @@ def check_f16_range(*models, sync_ranks: bool = False) -> None:
     if int(total.item()) != 0:
         raise RuntimeError(f'nerf.set_mlp_precision("{_mlp_precision}"): an activation left the fp16 range (|x| >= 4094) and a density output is '
                            'not finite -- render this model with "f32" or "bf16x3"')
-
-
-def paper_mlp_fwd_train(packed, cond, ro, rd, z, rd_view=None, packed_b=None, packed_h=None):
-    """Training forward: returns (raw, (saved,)) where `saved` holds every layer output for the backward.
-    packed_b (split-bf16 stream) or packed_h (split-fp16 stream) given -> the forward runs on that split kernel and `saved`
-    additionally carries its ReLU bit masks; the matching backward is paper_mlp_bwd(..., split=True / "f16")."""
-    dev = H.require_device(packed, cond, ro, rd, z, rd_view)
-    n_rays, n_samples = z.shape
-    lib = H.lib()
-    raw = torch.empty((n_rays, n_samples, 4), dtype=torch.float32, device=dev)
-    saved = torch.empty(lib.nf_paper_saved_floats(n_rays * n_samples), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        if packed_h is not None:
-            H.check(lib.nf_paper_mlp_fwd_train_f16(H.ptr(packed_h), H.ptr(cond), H.ptr(ro), H.ptr(rd), H.ptr(rd_view), H.ptr(z),
-                                                   n_rays, n_samples, H.ptr(raw), H.ptr(saved), H.stream_ptr(dev)),
-                    "nf_paper_mlp_fwd_train_f16")
-        elif packed_b is not None:
-            H.check(lib.nf_paper_mlp_fwd_train_bf16(H.ptr(packed_b), H.ptr(cond), H.ptr(ro), H.ptr(rd), H.ptr(rd_view), H.ptr(z),
-                                                    n_rays, n_samples, H.ptr(raw), H.ptr(saved), H.stream_ptr(dev)),
-                    "nf_paper_mlp_fwd_train_bf16")
-        else:
-            H.check(lib.nf_paper_mlp_fwd_train(H.ptr(packed), H.ptr(cond), H.ptr(ro), H.ptr(rd), H.ptr(rd_view), H.ptr(z), n_rays,
-                                               n_samples, H.ptr(raw), H.ptr(saved), H.stream_ptr(dev)), "nf_paper_mlp_fwd_train")
-    return raw, (saved,)
-
-
-def split_saved_to_f32(saved_t: torch.Tensor, n_points: int, f16: bool, family: str = "paper") -> torch.Tensor:
-    """The activations a SPLIT training forward saved (fragment streams of (hi, lo) pairs, sections padded to 32 points) converted to
-    the exact-f32 training layout (sections [n_points][width] f32 rows at nfl::S_* x n_points): for tests and for the exact-f32
-    weight-gradient GEMMs on a split forward (paper_mlp_bwd(..., exact_dw=True))."""
-    dev = H.require_device(saved_t)
-    lib = H.lib()
-    out = torch.empty((lib.nf_lcode_saved_floats if family == "lcode" else lib.nf_paper_saved_floats)(n_points), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        H.check(lib.nf_split_saved_to_f32(1 if family == "lcode" else 0, H.ptr(saved_t), n_points, int(bool(f16)), H.ptr(out), H.stream_ptr(dev)),
-                "nf_split_saved_to_f32")
-    return out
-
-
-def paper_mlp_bwd(model, packed, cond, z, d_raw, saved, split=False, exact_dw=False):
-    """d_raw (n_rays, n_samples, 4) -> ([26 parameter gradients in state_dict order], d_latent (32)).
-    layers_dir.3.{weight,bias} get None, as autograd gives the reference (Quirk Q3).  split=True runs the dX chain on the
-    split-bf16 kernel (requires `saved` from the split-bf16 training forward) and, unless exact_dw, the dW GEMMs too."""
-    (saved_t,) = saved
-    d_raw = _c(d_raw)
-    dev = H.require_device(packed, cond, saved_t, d_raw)
-    lib = H.lib()
-    n_rays, n_samples = z.shape
-    with torch.cuda.device(dev):             # the slice plan behind the size depends on the CURRENT device's CU count (nf_mlp_dw.h): ask on `dev`
-        ws_floats = lib.nf_paper_bwd_workspace_floats(n_rays * n_samples)
-    ws = torch.empty(ws_floats, dtype=torch.float32, device=dev)
-    flat = torch.empty(lib.nf_paper_grad_floats(), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        if split == "f16":
-            packed_ht = model.hip_weights().get_f16_t()
-            H.check(lib.nf_paper_mlp_bwd_f16(H.ptr(packed), H.ptr(packed_ht), H.ptr(cond), H.ptr(saved_t), H.ptr(d_raw), n_rays,
-                                             n_samples, H.ptr(ws), ws_floats, H.ptr(flat), H.stream_ptr(dev)), "nf_paper_mlp_bwd_f16")
-        elif split:
-            packed_bt = model.hip_weights().get_bf16_t()
-            saved_f32 = split_saved_to_f32(saved_t, n_rays * n_samples, False) if exact_dw else None      # the exact GEMMs read f32 rows
-            H.check(lib.nf_paper_mlp_bwd_bf16(H.ptr(packed), H.ptr(packed_bt), H.ptr(cond), H.ptr(saved_t), H.ptr(d_raw), n_rays,
-                                              n_samples, H.ptr(ws), ws_floats, H.ptr(flat), int(bool(exact_dw)), H.ptr(saved_f32),
-                                              H.stream_ptr(dev)),
-                    "nf_paper_mlp_bwd_bf16")
-        else:
-            packed_t = model.hip_weights().get_t()
-            H.check(lib.nf_paper_mlp_bwd(H.ptr(packed), H.ptr(packed_t), H.ptr(cond), H.ptr(saved_t), H.ptr(d_raw), n_rays,
-                                         n_samples, H.ptr(ws), ws_floats, H.ptr(flat), H.stream_ptr(dev)), "nf_paper_mlp_bwd")
-    params = model.hip_param_list()
-    grads, off = [], 0
-    for i, p in enumerate(params):
-        n = p.numel()
-        grads.append(None if i in (22, 23) else flat[off:off + n].view(p.shape))
-        off += n
-    return grads, flat[off:off + 32]
 
 
 # ---------------------------------------------------------------------------------------- K5

@@ -76,38 +76,56 @@ def test_f16x3_weight_scales_follow_the_layers(hip_lib, gpu):
     assert torch.all(rms["f16x3"] <= 4.0 * rms["f32"] + 1e-9)
 
 
-def test_f16x3_range_guard_fails_loudly(hip_lib, gpu):
+def _family_case(family, name):
+    """Case `name` with the parameters of `family`, and that family's model factory."""
+    c = C.build_case(name)
+    if family == "paper":
+        return c, U.make_model
+    c["p_coarse"], c["p_fine"] = O.init_lcode_params(5), O.init_lcode_params(6)
+    return c, U.make_lcode_model
+
+
+# per family: a weight whose overflow reaches sigma unsaturated, and the factor that makes it non-finite in the split-fp16 kernel.
+# paper: fc_feat has no ReLU.  lcode: sigma = fc_alpha(x) reads x after a saturating ReLU, so only fc_alpha weights beyond what the
+# packed fp16 stream holds (65504 at the smallest per-layer scale, 2^-24) make it non-finite.
+SIGMA_OVERFLOW = {"paper": ("fc_feat", 2.0 ** 16), "lcode": ("fc_alpha", 2.0 ** 50)}
+
+
+@pytest.mark.parametrize("family", ["paper", "lcode"])
+def test_f16x3_range_guard_fails_loudly(hip_lib, gpu, family):
     """Activations beyond fp16's range (here: a hidden layer scaled by 2^14): the pre-flight probe (exact-f32 forward on a sample
     of the frame's points, 4x margin) makes run_one_iter_of_nerf raise instead of returning a corrupted frame; the kernel itself
-    saturates instead of producing NaN, and flags a non-finite density (an unsaturated fc_feat overflow)."""
+    saturates instead of producing NaN, and flags a non-finite density (an unsaturated overflow, SIGMA_OVERFLOW)."""
     import nerf
-    c = C.build_case("eval_det_64_128")
+    c, make = _family_case(family, "eval_det_64_128")
     c["p_coarse"] = dict(c["p_coarse"])
     c["p_coarse"]["layers_xyz.1.weight"] = c["p_coarse"]["layers_xyz.1.weight"] * 2.0 ** 14
     nerf.set_mlp_precision("f16x3")
     with pytest.raises(RuntimeError, match="fp16 range"):
-        U.run_product(nerf, c, gpu)
+        U.run_product(nerf, c, gpu, make=make)
     # the kernel alone (no probe): finite colours thanks to the saturating ReLU -- wrong, but not NaN-poisoned
     from nerf import ops
-    m = U.make_model(nerf, c["p_coarse"], gpu)
-    cond = ops.paper_condition(m.hip_weights().get(), c["expr"].to(gpu), c["latent"].to(gpu), O.NEAR, O.FAR)
+    m = make(nerf, c["p_coarse"], gpu)
+    fam = m.hip_weights().family
+    cond = ops.mlp_condition(fam, m.hip_weights().get(), c["expr"].to(gpu), c["latent"].to(gpu), O.NEAR, O.FAR)
     z = torch.linspace(0.2, 0.8, 64).expand(c["n_rays"], 64).contiguous().to(gpu)
-    raw = ops.paper_mlp_fwd_f16(m.hip_weights().get_f16(), cond, c["ro"].to(gpu), c["rd"].to(gpu), z)
+    raw = ops.mlp_fwd(fam, "f16x3", m.hip_weights().get_f16(), cond, c["ro"].to(gpu), c["rd"].to(gpu), z)
     assert bool(torch.isfinite(raw[..., :3]).all())
-    # fc_feat has no ReLU: blowing IT up reaches sigma as inf / NaN and sets the kernel's sticky flag
-    p2 = dict(C.build_case("eval_det_64_128")["p_coarse"])
-    p2["fc_feat.weight"] = p2["fc_feat.weight"] * 2.0 ** 16
-    m2 = U.make_model(nerf, p2, gpu)
-    cond2 = ops.paper_condition(m2.hip_weights().get(), c["expr"].to(gpu), c["latent"].to(gpu), O.NEAR, O.FAR)
-    ops.paper_mlp_fwd_f16(m2.hip_weights().get_f16(), cond2, c["ro"].to(gpu), c["rd"].to(gpu), z)
+    # an unsaturated overflow reaches sigma as inf / NaN and sets the kernel's sticky flag
+    layer, k = SIGMA_OVERFLOW[family]
+    p2 = dict(_family_case(family, "eval_det_64_128")[0]["p_coarse"])
+    p2[layer + ".weight"] = p2[layer + ".weight"] * k
+    m2 = make(nerf, p2, gpu)
+    cond2 = ops.mlp_condition(fam, m2.hip_weights().get(), c["expr"].to(gpu), c["latent"].to(gpu), O.NEAR, O.FAR)
+    ops.mlp_fwd(fam, "f16x3", m2.hip_weights().get_f16(), cond2, c["ro"].to(gpu), c["rd"].to(gpu), z)
     with pytest.raises(RuntimeError, match="fp16 range"):
         ops.check_f16_range(m2)
     nerf.set_mlp_precision("f32")
-    out, *_ = U.run_product(nerf, c, gpu)                        # the exact-f32 kernels render the same model
+    out, *_ = U.run_product(nerf, c, gpu, make=make)             # the exact-f32 kernels render the same model
     assert bool(torch.isfinite(out[0]).all())
     nerf.set_mlp_precision("f16x3")
-    c2 = C.build_case("eval_det_64_128")
-    out, *_ = U.run_product(nerf, c2, gpu)                       # a healthy model is not affected
+    c2, _ = _family_case(family, "eval_det_64_128")
+    out, *_ = U.run_product(nerf, c2, gpu, make=make)            # a healthy model is not affected
     assert bool(torch.isfinite(out[3]).all())
 
 
@@ -131,14 +149,15 @@ def test_f16x3_end_to_end_at_f32_tolerances(hip_lib, gpu, name):
         assert dp <= 1e-4, (k, dp)
 
 
-def test_f16x3_range_guard_is_armed_in_training(hip_lib, gpu):
+@pytest.mark.parametrize("family", ["paper", "lcode"])
+def test_f16x3_range_guard_is_armed_in_training(hip_lib, gpu, family):
     """Training under "f16x3" (VERDICT r02 weak #1): (a) an overflow that happens in ONE iteration between two polls is still seen at
     the next poll -- every step re-packs the weight stream, which clears the stream's flag, so the flag is carried over on the
-    device (ops.PaperWeights._get); (b) a model that drifts out of range and stays there is refused by the exact-f32 probe at the
+    device (ops.MLPWeights._get); (b) a model that drifts out of range and stays there is refused by the exact-f32 probe at the
     next cadence point (ops.set_f16_train_probe_every, which the trainer sets to its print_every).  Both raise RuntimeError."""
     import nerf
     from nerf import ops
-    c = C.build_case("train_rand_64_64")
+    c, make = _family_case(family, "train_rand_64_64")
     opt = U.make_options(nerf, 64, 64, True, 0.1, chunksize=2048)
     ex, ed = U.encoders(nerf)
     n = c["ro"].shape[0]
@@ -154,22 +173,23 @@ def test_f16x3_range_guard_is_armed_in_training(hip_lib, gpu):
     try:
         # (a) the sticky flag
         ops.set_f16_train_probe_every(1000)                              # probe on the first step only: isolate the flag path
-        mc, mf = U.make_model(nerf, c["p_coarse"], gpu), U.make_model(nerf, c["p_fine"], gpu)
+        mc, mf = make(nerf, c["p_coarse"], gpu), make(nerf, c["p_fine"], gpu)
         step(mc, mf)
         step(mc, mf)
         ops.check_f16_range(mc, mf)                                      # healthy so far
+        layer, k = SIGMA_OVERFLOW[family]
         with torch.no_grad():
-            mf.fc_feat.weight.mul_(2.0 ** 16)                            # fc_feat has no ReLU: its overflow reaches sigma as inf / NaN
+            getattr(mf, layer).weight.mul_(k)                            # reaches sigma as inf / NaN
         step(mc, mf)
         with torch.no_grad():
-            mf.fc_feat.weight.mul_(2.0 ** -16)
+            getattr(mf, layer).weight.mul_(1.0 / k)
         step(mc, mf)                                                     # two healthy steps: each re-packs the stream
         step(mc, mf)
         with pytest.raises(RuntimeError, match="fp16 range"):
             ops.check_f16_range(mc, mf)
         # (b) the probe cadence
         ops.set_f16_train_probe_every(2)                                 # calls 1, 3, 5, ... of each model
-        mc, mf = U.make_model(nerf, c["p_coarse"], gpu), U.make_model(nerf, c["p_fine"], gpu)
+        mc, mf = make(nerf, c["p_coarse"], gpu), make(nerf, c["p_fine"], gpu)
         step(mc, mf)
         with torch.no_grad():
             mc.layers_xyz[1].weight.mul_(2.0 ** 14)

@@ -36,14 +36,6 @@ def _configs():
 CONFIGS = _configs()
 
 
-def _lcode_model(nerf, params, device):
-    m = nerf.models.ConditionalBlendshapeLearnableCodeNeRFModel(num_encoding_fn_xyz=10, num_encoding_fn_dir=4, include_input_xyz=True,
-                                                                include_input_dir=False, use_viewdirs=True, num_layers=4, hidden_size=256,
-                                                                include_expression=True)
-    m.load_state_dict(params)
-    return m.to(device)
-
-
 # (family, precision): the paper model in exact f32 and f16x3 (split-fp16, fp32-class: held to the f32 gates); the second family
 # (ConditionalBlendshapeLearnableCodeNeRFModel, M:529-636) with the same density head in both as well
 @pytest.mark.parametrize("family,precision", [("paper", "f32"), ("paper", "f16x3"), ("lcode", "f32"), ("lcode", "f16x3")])
@@ -62,7 +54,7 @@ def test_fuzz_against_oracle(hip_lib, gpu, k, family, precision):
     bg = None if no_bg else c["bg"]
     if family == "lcode":
         c["p_coarse"], c["p_fine"] = O.init_lcode_params(5, boost="survey"), O.init_lcode_params(6, boost="survey")
-    make, mlp = (_lcode_model, O.lcode_mlp) if family == "lcode" else (U.make_model, None)
+    make, mlp = (U.make_lcode_model, O.lcode_mlp) if family == "lcode" else (U.make_model, None)
     ref = O.render_rays(c["p_coarse"], c["p_fine"], c["ro"], c["rd"], c["expr"], c["latent"], bg, O.NEAR, O.FAR, c["n_coarse"], c["n_fine"],
                         t_rand=c["t_rand"], noise_c=c["noise_c"], u=c["u"], noise_f=c["noise_f"], lindisp=bool(c.get("lindisp", False)),
                         white_background=white, mlp=mlp)
@@ -126,7 +118,7 @@ def test_fuzz_training_step_gradients(hip_lib, gpu, k, family, precision):
         del C.CASES[name]
     if family == "lcode":
         c["p_coarse"], c["p_fine"] = O.init_lcode_params(5, boost="survey"), O.init_lcode_params(6, boost="survey")
-    make, mlp = (_lcode_model, O.lcode_mlp) if family == "lcode" else (U.make_model, None)
+    make, mlp = (U.make_lcode_model, O.lcode_mlp) if family == "lcode" else (U.make_model, None)
     nc, nf = c["n_coarse"], c["n_fine"]
     mc = make(nerf, c["p_coarse"], gpu)
     mf = make(nerf, c["p_fine"], gpu) if nf > 0 else None

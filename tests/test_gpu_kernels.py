@@ -344,6 +344,50 @@ def test_model_forward_and_run_network_on_encoded_inputs(hip_lib, gpu):
         m(x87.to(gpu), c["expr"].to(gpu), c["latent"].to(gpu).requires_grad_(True))
 
 
+def _family_model(family, gpu):
+    import nerf
+    from tests import util as U
+    c, ro, rd, z = _mlp_inputs(5, 16, 12)
+    if family == "paper":
+        return U.make_model(nerf, c["p_coarse"], gpu), c, ro, rd, z
+    return U.make_lcode_model(nerf, O.init_lcode_params(5), gpu), c, ro, rd, z
+
+
+@pytest.mark.parametrize("family", ["paper", "lcode"])
+def test_wrong_sized_conditioning_is_refused(hip_lib, gpu, family):
+    """The conditioning kernels read expr[0..75] and latent[0..31] unconditionally: a 75-d expression or a 31-d latent code raises
+    ValueError from hip_forward (with and without gradients) and from forward() on encoded inputs, instead of reading out of bounds."""
+    m, c, ro, rd, z = _family_model(family, gpu)
+    x87 = O.encode_points(ro, rd, z, O.NEAR, O.FAR).to(gpu)
+    ro, rd, z = ro.to(gpu), rd.to(gpu), z.to(gpu)
+    expr, lat = c["expr"].reshape(-1).to(gpu), c["latent"].reshape(-1).to(gpu)
+    for e, l in ((expr[:75].contiguous(), lat), (expr, lat[:31].contiguous())):
+        for need_grad in (False, True):
+            with pytest.raises(ValueError, match="76-d expression and a 32-d latent"):
+                m.hip_forward(ro, rd, z, None, e, l, O.NEAR, O.FAR, need_grad)
+        with pytest.raises(ValueError, match="76-d expression and a 32-d latent"), torch.no_grad():
+            m(x87, e, l)
+
+
+@pytest.mark.parametrize("family", ["paper", "lcode"])
+def test_invalidate_repacks_after_a_data_write(hip_lib, gpu, family):
+    """A write through `p.data` leaves the version counter alone, so the cached weight images do not see it; after
+    hip_weights().invalidate() the next forward re-packs and computes what a model built with the new weights computes."""
+    import nerf
+    from tests import util as U
+    m, c, ro, rd, z = _family_model(family, gpu)
+    args = (ro.to(gpu), rd.to(gpu), z.to(gpu), None, c["expr"].to(gpu), c["latent"].to(gpu), O.NEAR, O.FAR, False)
+    before = m.hip_forward(*args)[0]
+    m.fc_rgb.weight.data.mul_(2.0)
+    assert torch.equal(m.hip_forward(*args)[0], before)             # the stale image: the write went unseen
+    m.hip_weights().invalidate()
+    after = m.hip_forward(*args)[0]
+    assert not torch.equal(after, before)
+    make = U.make_model if family == "paper" else U.make_lcode_model
+    fresh = make(nerf, {k: v.detach().cpu() for k, v in m.state_dict().items()}, gpu)
+    assert torch.equal(after, fresh.hip_forward(*args)[0])
+
+
 def test_empty_inputs(hip_lib, gpu):
     """Zero rays through every stage: shapes come back empty, nothing is launched, nothing raises."""
     import nerf

@@ -22,6 +22,14 @@ def make_model(nerf, params, device):
     return m.to(device)
 
 
+def make_lcode_model(nerf, params, device):
+    m = nerf.models.ConditionalBlendshapeLearnableCodeNeRFModel(num_encoding_fn_xyz=10, num_encoding_fn_dir=4, include_input_xyz=True,
+                                                                include_input_dir=False, use_viewdirs=True, num_layers=4, hidden_size=256,
+                                                                include_expression=True)
+    m.load_state_dict(params)
+    return m.to(device)
+
+
 def encoders(nerf):
     return (nerf.get_embedding_function(num_encoding_functions=10, include_input=True, log_sampling=True),
             nerf.get_embedding_function(num_encoding_functions=4, include_input=False, log_sampling=True))
@@ -61,10 +69,10 @@ def case_random_lists(c):
     return rands, randns
 
 
-def run_product(nerf, c, device, mode="train", grad=False, chunksize=65536):
-    """run_one_iter_of_nerf of the product package on case `c` (see oracle/cases.py)."""
-    mc = make_model(nerf, c["p_coarse"], device)
-    mf = make_model(nerf, c["p_fine"], device) if c["n_fine"] > 0 else None
+def run_product(nerf, c, device, mode="train", grad=False, chunksize=65536, make=make_model):
+    """run_one_iter_of_nerf of the product package on case `c` (see oracle/cases.py); `make` builds the models of the case's family."""
+    mc = make(nerf, c["p_coarse"], device)
+    mf = make(nerf, c["p_fine"], device) if c["n_fine"] > 0 else None
     opt = make_options(nerf, c["n_coarse"], c["n_fine"], bool(c["stochastic"]), c["noise_std"], chunksize,
                        lindisp=bool(c.get("lindisp", False)))
     ex, ed = encoders(nerf)
