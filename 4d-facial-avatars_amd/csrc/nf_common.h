@@ -31,6 +31,27 @@ static inline int64_t nf_cu_count() {
 }
 
 
+// Argument check and grid of the fused-MLP forward entry points, before anything touches the device: empty work returns 0, NULL
+// pointers or impossible sizes NF_EINVAL; otherwise launch(n_points, grid) runs with one workgroup per 128 points.  The training
+// modes require `saved`, whose sections are addressed with 32-bit byte offsets (a larger launch would wrap the buffer descriptor to
+// an empty range and drop every save without an error): the exact-f32 layout bounds n_points, the split layout n_points padded to 32.
+enum NfFwdMode { NF_FWD_INFER, NF_FWD_TRAIN_F32, NF_FWD_TRAIN_SPLIT };
+
+template <class Launch>
+static inline int nf_mlp_fwd_launch(NfFwdMode mode, const void* w, const float* cond, const float* ro, const float* rd, const float* z,
+                                    const float* raw, const float* saved, int64_t n_rays, int n_samples, Launch launch) {
+    if (n_rays == 0 && n_samples > 0) return 0;            // nothing to do (empty tensors have NULL data pointers)
+    if (!w || !cond || !ro || !rd || !z || !raw || (mode != NF_FWD_INFER && !saved) || n_rays < 0 || n_samples <= 0) return NF_EINVAL;
+    const int64_t n_points = n_rays * n_samples;
+    if (n_points == 0) return 0;
+    const int64_t grid = (n_points + 127) / 128;
+    if (grid > 0x7fffffff) return NF_EINVAL;
+    const int64_t section = mode == NF_FWD_TRAIN_SPLIT ? (n_points + 31) & ~(int64_t)31 : n_points;
+    if (mode != NF_FWD_INFER && section >= ((int64_t)1 << 22)) return NF_EINVAL;
+    launch(n_points, (unsigned)grid);
+    NF_RETURN_LAUNCH();
+}
+
 // IEEE single ops that must not be contracted into FMAs (bit parity with the reference's
 // separate mul / add tensor ops).  The library is also built with -ffp-contract=off.
 __device__ __forceinline__ float nf_mul(float a, float b) { return __fmul_rn(a, b); }

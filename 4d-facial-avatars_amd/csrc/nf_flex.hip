@@ -61,17 +61,12 @@ struct NfFlex {
 template <int NH>
 static void nf_flex_table(std::vector<uint32_t>& t) {
     using L = NfFlex<NH>;
-    t.assign(L::PACKED, 0xFF000000u);
+    t.assign(L::PACKED, NF_ZERO_CODE);
     auto fill = [&](int off, int nk, int no_tiles, int tensor, int n_out, int n_cols, bool pe) {
-        for (int ni = 0; ni < nk; ++ni)
-            for (int no = 0; no < no_tiles; ++no)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int r = 0; r < 4; ++r) {
-                        const int g = lane >> 4, i = lane & 15, n = 16 * no + i, slot = 16 * ni + 4 * g + r;
-                        const int col = pe ? nfl::pe_slot_to_col(slot) : slot;
-                        if (n < n_out && col >= 0)
-                            t[(size_t)off + ((size_t)(ni * no_tiles + no) * 64 + lane) * 4 + r] = ((uint32_t)tensor << 24) | (uint32_t)(n * n_cols + col);
-                    }
+        nf_fill_frag(t, off, nk, no_tiles, [&](int slot, int n) {
+            const int col = pe ? nfl::pe_slot_to_col(slot) : slot;
+            return n < n_out && col >= 0 ? nf_code(tensor, n, col, n_cols) : NF_ZERO_CODE;
+        });
     };
     fill(L::OFF_1, 4, 8, 0, 128, 63, true);
     for (int k = 0; k < NH; ++k) fill(L::off_h(k), 8, 8, 2 + 2 * k, 128, 128, false);
@@ -85,16 +80,8 @@ static void nf_flex_table(std::vector<uint32_t>& t) {
 template <int NH>
 static void nf_flex_table_t(std::vector<uint32_t>& t) {
     using L = NfFlex<NH>;
-    t.assign(L::PACKED_T, 0xFF000000u);
-    auto fill = [&](int off, int nk, int no_tiles, int tensor, int n_rows, int n_cols) {
-        for (int ni = 0; ni < nk; ++ni)
-            for (int no = 0; no < no_tiles; ++no)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int r = 0; r < 4; ++r) {
-                        const int g = lane >> 4, i = lane & 15, row = 16 * ni + 4 * g + r, col = 16 * no + i;
-                        if (row < n_rows) t[(size_t)off + ((size_t)(ni * no_tiles + no) * 64 + lane) * 4 + r] = ((uint32_t)tensor << 24) | (uint32_t)(row * n_cols + col);
-                    }
-    };
+    t.assign(L::PACKED_T, NF_ZERO_CODE);
+    auto fill = [&](int off, int nk, int no_tiles, int tensor, int n_rows, int n_cols) { nf_fill_frag_t(t, off, nk, no_tiles, tensor, n_rows, n_cols); };
     fill(L::OFFT_O, 1, 8, 2 + 2 * NH, 4, 128);                                        // fc_out.weight (4, 128)
     for (int k = 0; k < NH; ++k) fill(L::offt_h(k), 8, 8, 2 + 2 * k, 128, 128);       // layers_xyz[k].weight (128, 128)
 }

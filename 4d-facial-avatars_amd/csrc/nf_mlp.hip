@@ -26,9 +26,6 @@
 // pack: gather the 26 nn.Parameter storages into the fragment-ordered image
 // =================================================================================================
 
-static const uint32_t NF_ZERO_CODE = 0xFF000000u;
-static inline uint32_t nf_code(int tensor, int row, int col, int ncols) { return ((uint32_t)tensor << 24) | (uint32_t)(row * ncols + col); }
-
 // state_dict ids (NF_PAPER_NUM_PARAMS order)
 enum { ID_XYZ0_W = 0, ID_XYZ0_B = 1, ID_FEAT_W = 12, ID_FEAT_B = 13, ID_ALPHA_W = 14, ID_ALPHA_B = 15, ID_DIR0_W = 16,
        ID_DIR0_B = 17, ID_RGB_W = 24, ID_RGB_B = 25 };
@@ -38,21 +35,13 @@ enum { ID_XYZ0_W = 0, ID_XYZ0_B = 1, ID_FEAT_W = 12, ID_FEAT_B = 13, ID_ALPHA_W 
 template <class ColFn>
 static void nf_fill_layer(std::vector<uint32_t>& t, int off, int nk, int no_tiles, int tensor, int n_out, int n_cols,
                           ColFn col_of, int alpha_row = -1) {
-    for (int ni = 0; ni < nk; ++ni)
-        for (int no = 0; no < no_tiles; ++no)
-            for (int lane = 0; lane < 64; ++lane)
-                for (int r = 0; r < 4; ++r) {
-                    const int g = lane >> 4, i = lane & 15;
-                    const int n = 16 * no + i, slot = 16 * ni + 4 * g + r;
-                    uint32_t code = NF_ZERO_CODE;
-                    if (n < n_out) {
-                        const int col = col_of(slot);
-                        if (col >= 0) code = nf_code(tensor, n, col, n_cols);
-                    } else if (n == alpha_row) {
-                        if (slot < 256) code = nf_code(ID_ALPHA_W, 0, slot, 256);   // fc_alpha reads feat only
-                    }
-                    t[(size_t)off + ((size_t)(ni * no_tiles + no) * 64 + lane) * 4 + r] = code;
-                }
+    nf_fill_frag(t, off, nk, no_tiles, [&](int slot, int n) {
+        if (n < n_out) {
+            const int col = col_of(slot);
+            return col >= 0 ? nf_code(tensor, n, col, n_cols) : NF_ZERO_CODE;
+        }
+        return n == alpha_row && slot < 256 ? nf_code(ID_ALPHA_W, 0, slot, 256) : NF_ZERO_CODE;   // fc_alpha reads feat only
+    });
 }
 
 static void nf_build_gather_table(std::vector<uint32_t>& t) {
@@ -514,27 +503,23 @@ k_paper_mlp_fwd_save(const float* __restrict__ packed, const float* __restrict__
 
 static int nf_launch_fwd(const float* packed, const float* cond, const float* ro, const float* rd, const float* rd_view,
                          const float* z, int64_t n_rays, int n_samples, float* raw, float* saved, nf_stream_t stream) {
-    if (n_rays == 0 && n_samples > 0) return 0;            // nothing to do (empty tensors have NULL data pointers)
-    if (!packed || !cond || !ro || !rd || !z || !raw || n_rays < 0 || n_samples <= 0) return NF_EINVAL;
-    const int64_t n_points = n_rays * n_samples;
-    if (n_points == 0) return 0;
     constexpr int NT = NF_MLP_NT;
-    const int64_t per_block = (int64_t)NF_MLP_WAVES * 16 * NT;
-    const int64_t grid = (n_points + per_block - 1) / per_block;
-    if (grid > 0x7fffffff) return NF_EINVAL;
-    if (saved && n_points >= ((int64_t)1 << 22)) return NF_EINVAL;       // the save path addresses a section with 32-bit byte offsets (1 KiB per point)
-    if (saved)
-        hipLaunchKernelGGL((k_paper_mlp_fwd_save<NT>), dim3((unsigned)grid), dim3(64 * NF_MLP_WAVES), 0, nf_s(stream), packed,
-                           cond, ro, rd, rd_view ? rd_view : rd, z, n_points, n_samples, raw, saved);
-    else
+    static_assert(NF_MLP_WAVES * 16 * NT == 128, "nf_mlp_fwd_launch sizes the grid for 128 points per workgroup");
+    const float* rdv = rd_view ? rd_view : rd;
+    return nf_mlp_fwd_launch(saved ? NF_FWD_TRAIN_F32 : NF_FWD_INFER, packed, cond, ro, rd, z, raw, saved, n_rays, n_samples,
+                             [&](int64_t n_points, unsigned grid) {
+        if (saved)
+            hipLaunchKernelGGL((k_paper_mlp_fwd_save<NT>), dim3(grid), dim3(64 * NF_MLP_WAVES), 0, nf_s(stream), packed, cond, ro, rd, rdv, z,
+                               n_points, n_samples, raw, saved);
+        else                                                    // inference: a persistent grid, at most one workgroup per CU
 #if NF_F32_RR
-        hipLaunchKernelGGL((k_paper_mlp_fwd_rr<NT>), dim3((unsigned)(grid < nf_cu_count() ? grid : nf_cu_count())), dim3(64 * NF_MLP_WAVES), 0, nf_s(stream), packed,
-                           cond, ro, rd, rd_view ? rd_view : rd, z, n_points, n_samples, raw);
+            hipLaunchKernelGGL((k_paper_mlp_fwd_rr<NT>), dim3((unsigned)(grid < nf_cu_count() ? grid : nf_cu_count())), dim3(64 * NF_MLP_WAVES), 0,
+                               nf_s(stream), packed, cond, ro, rd, rdv, z, n_points, n_samples, raw);
 #else
-        hipLaunchKernelGGL((k_paper_mlp_fwd<NT>), dim3((unsigned)(grid < nf_cu_count() ? grid : nf_cu_count())), dim3(64 * NF_MLP_WAVES), 0, nf_s(stream), packed,
-                           cond, ro, rd, rd_view ? rd_view : rd, z, n_points, n_samples, raw);
+            hipLaunchKernelGGL((k_paper_mlp_fwd<NT>), dim3((unsigned)(grid < nf_cu_count() ? grid : nf_cu_count())), dim3(64 * NF_MLP_WAVES), 0,
+                               nf_s(stream), packed, cond, ro, rd, rdv, z, n_points, n_samples, raw);
 #endif
-    NF_RETURN_LAUNCH();
+    });
 }
 
 extern "C" int nf_paper_mlp_fwd(const float* packed, const float* cond, const float* ro, const float* rd, const float* rd_view,

@@ -6,31 +6,20 @@
 // the weight-gradient GEMMs (split-bf16: nf_mlp_bf16_dw.hip; exact f32: nf_mlp_dw.h).
 #include <vector>
 #include <mutex>
-#include "nf_common.h"
+#include "nf_mlp_split_common.h"
 #include "nf_mlp_layout.h"
 
 // NFB_F16 = 1 (nf_mlp_f16_bwd.hip includes this file): the same chain on fp16 operand pairs -- transposed weight stream with
 // per-layer power-of-two scales (nf_pack.h), gradients carried times a per-POINT power of two chosen layer by layer from the
 // point's largest gradient (block floating point, nf_mlp_bf16_machinery.inc) so that they sit at the top of fp16's exponent range.
-#ifndef NFB_F16
-#define NFB_F16 0
-#endif
 #if NFB_F16
-typedef _Float16 nfb_elt;
-typedef _Float16 bf16x8 __attribute__((ext_vector_type(8)));
-#define NFB_MFMA __builtin_amdgcn_mfma_f32_32x32x16_f16
 #define NFB_BWD_NAME(x) x##_f16
 #ifndef NFB_TILE_GROUP
 #define NFB_TILE_GROUP 4
 #endif
 #else
-typedef __bf16 nfb_elt;
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-#define NFB_MFMA __builtin_amdgcn_mfma_f32_32x32x16_bf16
 #define NFB_BWD_NAME(x) x##_bf16
 #endif
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 namespace nfb {
@@ -43,7 +32,6 @@ constexpr int NO[NL] = {4, 4, 4, 8, 8, 8, 8, 8, 8, 8};
 constexpr int pair_off(int l) { int o = 0; for (int i = 0; i < l; ++i) o += KS[i] * NO[i]; return o; }
 constexpr int N_PAIRS = pair_off(NL);
 constexpr int STREAM_BF16 = N_PAIRS * 2 * 512;
-__host__ __device__ constexpr int hid_feature(int s, int h, int j) { return 16 * s + 4 * h + (j & 3) + 8 * (j >> 2); }
 }  // namespace nfb
 
 #include "nf_mlp_bf16_machinery.inc"
@@ -52,12 +40,10 @@ __host__ __device__ constexpr int hid_feature(int s, int h, int j) { return 16 *
 // =================================================================================================
 // transposed (hi, lo) stream: block (s, nt), lane (h', i), j  ->  W[row = reduction feature(s, h', j)][col0 + 32 nt + i]
 // =================================================================================================
-static const uint32_t NF_ZERO_BT = 0xFF000000u;
 
 static void nf_build_table_bf16_t(std::vector<uint32_t>& t) {
     using namespace nfb;
-    t.assign((size_t)N_PAIRS * 512, NF_ZERO_BT);
-    auto code = [](int tensor, int row, int col, int ncols) { return ((uint32_t)tensor << 24) | (uint32_t)(row * ncols + col); };
+    t.assign((size_t)N_PAIRS * 512, NF_ZERO_CODE);
     // per layer: (tensor, rows valid, ncols, col0)
     const int tensor[NL] = {24, 20, 18, 16, 12, 10, 8, 6, 4, 2};
     const int nrows[NL] = {3, 128, 128, 128, 256, 256, 256, 256, 256, 256};
@@ -69,15 +55,15 @@ static void nf_build_table_bf16_t(std::vector<uint32_t>& t) {
                 for (int lane = 0; lane < 64; ++lane)
                     for (int j = 0; j < 8; ++j) {
                         const int h = lane >> 5, i = lane & 31, col = col0[l] + 32 * nt + i;
-                        uint32_t c = NF_ZERO_BT;
+                        uint32_t c = NF_ZERO_CODE;
                         if (l == 0) {                                   // slots (s = 0, h = 0, j = 0..2) carry d r, d g, d b
-                            if (s == 0 && h == 0 && j < 3) c = code(24, j, col, 128);
+                            if (s == 0 && h == 0 && j < 3) c = nf_code(24, j, col, 128);
                         } else if (l == 3) {                            // k-steps 0..7: dZ of layers_dir.0; k-step 8, slot (0, 0): d sigma
-                            if (s < 8) c = code(16, hid_feature(s, h, j), col, 280);
-                            else if (s == 8 && h == 0 && j == 0) c = code(14, 0, col, 256);
+                            if (s < 8) c = nf_code(16, hid_feature(s, h, j), col, 280);
+                            else if (s == 8 && h == 0 && j == 0) c = nf_code(14, 0, col, 256);
                         } else {
                             const int row = hid_feature(s, h, j);
-                            if (row < nrows[l]) c = code(tensor[l], row, col, ncols[l]);
+                            if (row < nrows[l]) c = nf_code(tensor[l], row, col, ncols[l]);
                         }
                         t[((size_t)(pair_off(l) + s * NO[l] + nt)) * 512 + lane * 8 + j] = c;
                     }
@@ -285,12 +271,5 @@ int NFB_BWD_NAME(nfb_launch_bwd_chain)(const void* packed_t, const float* saved,
 #if !NFB_F16
 // host-only: the gather table of this stream (one 32-bit code per bf16 element of the hi blocks: tensor id << 24 | element
 // offset, 0xFF000000 = zero) for tests/test_host.py; out == NULL returns the number of entries.  Transposed (backward-chain) stream of the paper model.
-extern "C" long nf_paper_stream_table_bwd_bf16(uint32_t* out, size_t n_entries) {
-    std::vector<uint32_t> t;
-    nf_build_table_bf16_t(t);
-    if (!out) return (long)t.size();
-    if (n_entries != t.size()) return -1;
-    for (size_t i = 0; i < t.size(); ++i) out[i] = t[i];
-    return (long)t.size();
-}
+extern "C" long nf_paper_stream_table_bwd_bf16(uint32_t* out, size_t n_entries) { return nf_export_table(nf_build_table_bf16_t, out, n_entries); }
 #endif

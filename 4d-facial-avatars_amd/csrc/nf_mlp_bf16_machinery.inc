@@ -1,6 +1,6 @@
 // Table-driven machinery of the split-bf16 fused MLP kernels (weight-stream -> LDS ring, stage/layer drivers, operand split,
 // activation saves).  Included by the forward (nf_mlp_bf16_kernel.inc) and backward-chain (nf_mlp_bf16_bwd.hip) kernels after
-// a header that defines namespace nfb { NL, KS[], NO[], pair_off() } for THEIR weight stream.
+// nf_mlp_split_common.h and a header that defines namespace nfb { NL, KS[], NO[], pair_off() } for THEIR weight stream.
 // =================================================================================================
 // forward
 // =================================================================================================
@@ -9,10 +9,6 @@
 // end-of-stage wait is a COUNTED s_waitcnt vmcnt(n) that leaves exactly that newest group in flight across the
 // (raw) workgroup barrier.  Per-call biases are DMA'd once into LDS so that no ordinary global load (whose
 // compiler-inserted vmcnt(0) would drain the pipeline) remains in the layer loop.  All LDS lives in ONE array.
-#ifndef NFB_MFMA                                    // translation units that predate the element-type switch: bf16
-typedef __bf16 nfb_elt;
-#define NFB_MFMA __builtin_amdgcn_mfma_f32_32x32x16_bf16
-#endif
 #ifndef NFB_KPS
 #define NFB_KPS 2                                   // k-steps per stage
 #endif

@@ -16,43 +16,28 @@
 #include <mutex>
 #include "nf_mlp_dev.h"
 #include "nf_mlp_stream.h"
-#include "nf_mlp_dw.h"
+#include "nf_mlp_bwd.h"
 #include "nf_pack.h"
 
 
 // =================================================================================================
 // transposed pack
 // =================================================================================================
-static const uint32_t NF_ZERO_CODE_T = 0xFF000000u;
-static inline uint32_t nf_code_t(int tensor, int row, int col, int ncols) { return ((uint32_t)tensor << 24) | (uint32_t)(row * ncols + col); }
-
-// block (ni, no), lane (g, i), r  ->  W[row = 16 ni + 4 g + r][col0 + 16 no + i]
-static void nf_fill_layer_t(std::vector<uint32_t>& t, int off, int nk, int no_tiles, int tensor, int n_rows, int n_cols, int col0) {
-    for (int ni = 0; ni < nk; ++ni)
-        for (int no = 0; no < no_tiles; ++no)
-            for (int lane = 0; lane < 64; ++lane)
-                for (int r = 0; r < 4; ++r) {
-                    const int g = lane >> 4, i = lane & 15;
-                    const int row = 16 * ni + 4 * g + r, col = col0 + 16 * no + i;
-                    t[(size_t)off + ((size_t)(ni * no_tiles + no) * 64 + lane) * 4 + r] =
-                        row < n_rows ? nf_code_t(tensor, row, col, n_cols) : NF_ZERO_CODE_T;
-                }
-}
-
+// block (ni, no), lane (g, i), r  ->  W[row = 16 ni + 4 g + r][col0 + 16 no + i]   (nf_pack.h: nf_fill_frag_t)
 static void nf_build_gather_table_t(std::vector<uint32_t>& t) {
     using namespace nfl;
-    t.assign(PACKED_T_FLOATS, NF_ZERO_CODE_T);
-    nf_fill_layer_t(t, OFFT_RGB, 1, 8, 24, 3, 128, 0);            // fc_rgb.weight (3,128)
-    nf_fill_layer_t(t, OFFT_D2, 8, 8, 20, 128, 128, 0);           // layers_dir.2
-    nf_fill_layer_t(t, OFFT_D1, 8, 8, 18, 128, 128, 0);           // layers_dir.1
-    nf_fill_layer_t(t, OFFT_D0, 8, 16, 16, 128, 280, 0);          // layers_dir.0[:, :256]
-    nf_fill_layer_t(t, OFFT_D0 + 8 * 16 * FRAG, 1, 16, 14, 1, 256, 0);   // chunk 8: slot 0 = fc_alpha.weight (1,256)
-    nf_fill_layer_t(t, OFFT_FEAT, 16, 16, 12, 256, 256, 0);       // fc_feat
-    nf_fill_layer_t(t, OFFT_L5, 16, 16, 10, 256, 256, 0);
-    nf_fill_layer_t(t, OFFT_L4, 16, 16, 8, 256, 256, 0);
-    nf_fill_layer_t(t, OFFT_L3, 16, 16, 6, 256, 427, 171);        // layers_xyz.3[:, 171:427]
-    nf_fill_layer_t(t, OFFT_L2, 16, 16, 4, 256, 256, 0);
-    nf_fill_layer_t(t, OFFT_L1, 16, 16, 2, 256, 256, 0);
+    t.assign(PACKED_T_FLOATS, NF_ZERO_CODE);
+    nf_fill_frag_t(t, OFFT_RGB, 1, 8, 24, 3, 128, 0);            // fc_rgb.weight (3,128)
+    nf_fill_frag_t(t, OFFT_D2, 8, 8, 20, 128, 128, 0);           // layers_dir.2
+    nf_fill_frag_t(t, OFFT_D1, 8, 8, 18, 128, 128, 0);           // layers_dir.1
+    nf_fill_frag_t(t, OFFT_D0, 8, 16, 16, 128, 280, 0);          // layers_dir.0[:, :256]
+    nf_fill_frag_t(t, OFFT_D0 + 8 * 16 * FRAG, 1, 16, 14, 1, 256, 0);   // chunk 8: slot 0 = fc_alpha.weight (1,256)
+    nf_fill_frag_t(t, OFFT_FEAT, 16, 16, 12, 256, 256, 0);       // fc_feat
+    nf_fill_frag_t(t, OFFT_L5, 16, 16, 10, 256, 256, 0);
+    nf_fill_frag_t(t, OFFT_L4, 16, 16, 8, 256, 256, 0);
+    nf_fill_frag_t(t, OFFT_L3, 16, 16, 6, 256, 427, 171);        // layers_xyz.3[:, 171:427]
+    nf_fill_frag_t(t, OFFT_L2, 16, 16, 4, 256, 256, 0);
+    nf_fill_frag_t(t, OFFT_L1, 16, 16, 2, 256, 256, 0);
 }
 
 static NfPackTable g_paper_table_t;
@@ -336,108 +321,81 @@ int nfb_launch_dw_gemm_bf16(int model, const float* dz, const float* d_raw, cons
 int nfb_launch_dw_gemm_f16(int model, const float* dz, const float* d_raw, const float* saved, int64_t n_points, int64_t pts_per_slice,
                            int n_slices, float* slabs, const float* gscale, nf_stream_t stream);
 
-extern "C" size_t nf_paper_bwd_workspace_floats(int64_t n_points) {
+// =================================================================================================
+// the backward driver of both families (nf_mlp_bwd.h)
+// =================================================================================================
+size_t nf_bwd_workspace_floats(const NfBwdFamily& fam, int64_t n_points) {
     int64_t pps; int ns, ns_b;
-    nfb_dw_plan(0, n_points, &pps, &ns);
-    NfDwGroup groups[NF_DW_GROUPS];
-    nf_build_dw_groups(groups);
-    ns_b = nf_dw_plan_groups(groups, NF_DW_GROUPS, n_points);
+    nfb_dw_plan(fam.model, n_points, &pps, &ns);
+    NfDwGroup groups[NF_DW_MAX_GROUPS];
+    fam.build_groups(groups);
+    ns_b = nf_dw_plan_groups(groups, fam.n_groups, n_points);
     if (ns_b > ns) ns = ns_b;
-    return (size_t)nfl::DZ_PER_POINT * (size_t)n_points + (size_t)(ns + 1) * nfl::SLAB_FLOATS + 16;      // + max |gradient| per dz section (fp16 kernels)
+    return (size_t)fam.dz_per_point * (size_t)n_points + (size_t)(ns + 1) * fam.slab_floats + 16;      // + max |gradient| per dz section (fp16 kernels)
 }
 
-
-// defined in nf_mlp_bf16_bwd.hip / nf_mlp_f16_bwd.hip
-int nfb_launch_bwd_chain_bf16(const void* packed_t, const float* saved, const float* d_raw, int64_t n_points, float* dz,
-                              float* gscale, nf_stream_t stream);
-int nfb_launch_bwd_chain_f16(const void* packed_t, const float* saved, const float* d_raw, int64_t n_points, float* dz,
-                             float* gscale, nf_stream_t stream);
-
-// packed_t (exact f32 chain) | packed_t_bf16 (split-bf16 chain) | packed_t_f16 (split-fp16 chain + dW): exactly one non-NULL
-static int nf_bwd_impl(const float* packed, const float* packed_t, const void* packed_t_bf16, const void* packed_t_f16, bool split_dw,
-                       const float* cond, const float* saved, const float* d_raw, int64_t n_rays, int n_samples, float* workspace,
-                       size_t workspace_floats, float* grads, nf_stream_t stream, float* stage_ms = nullptr, const float* saved_f32 = nullptr) {
-    // saved_f32: split chain + exact-f32 weight-gradient GEMMs only -- the split forward's activations converted to the exact-f32
-    // layout (nf_split_saved_to_f32); the chain reads its bit masks from `saved`, the GEMMs their operands from `saved_f32`
-    using namespace nfl;
-    if (!packed || (!packed_t && !packed_t_bf16 && !packed_t_f16) || !cond || !saved || !d_raw || !workspace || !grads || n_rays <= 0 ||
-        n_samples <= 0)
+int nf_bwd_run(const NfBwdFamily& fam, int precision, const float* packed, const void* packed_t, const float* cond, const float* saved,
+               const float* d_raw, int64_t n_rays, int n_samples, float* workspace, size_t workspace_floats, float* grads,
+               nf_stream_t stream, float* stage_ms, const float* saved_f32) {
+    if (!packed || !packed_t || !cond || !saved || !d_raw || !workspace || !grads || n_rays <= 0 || n_samples <= 0 || precision < 0 ||
+        precision > 2)
         return NF_EINVAL;
-    if (packed_t_f16) split_dw = true;
-    if ((packed_t_bf16 || packed_t_f16) && !split_dw && !saved_f32) return NF_EINVAL;
+    const bool split_dw = precision != 0 && !saved_f32;
     const int64_t n_points = n_rays * n_samples;
-    if (workspace_floats < nf_paper_bwd_workspace_floats(n_points)) return NF_EINVAL;
-    if (((n_points + 31) & ~(int64_t)31) >= ((int64_t)1 << 22)) return NF_EINVAL;   // as the training forward: 32-bit byte offsets into a (32-padded) section
+    const size_t need = nf_bwd_workspace_floats(fam, n_points);
+    if (workspace_floats < need) return NF_EINVAL;
+    // as the training forward: 32-bit byte offsets into a (32-padded) section; also bounds every grid below
+    if (((n_points + 31) & ~(int64_t)31) >= ((int64_t)1 << 22)) return NF_EINVAL;
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);
     if (e != hipSuccess) return (int)e;
     if (dev < 0 || dev >= 64) return NF_EINVAL;
-    int64_t pps; int ns;
+    int64_t pps = 0; int ns;
     NfDwGroupSet gset;
-    if (split_dw) nfb_dw_plan(0, n_points, &pps, &ns);
-    else {
-        nf_build_dw_groups(gset.g);
-        for (int k = 0; k <= NF_DW_MAX_GROUPS; ++k) gset.first_block[k] = 0x7fffffff;
-        ns = nf_dw_plan_groups(gset.g, NF_DW_GROUPS, n_points, gset.first_block);
-        pps = 0;
-    }
-    float* dz = workspace;
-    float* slabs = workspace + (size_t)DZ_PER_POINT * n_points;
-    float* sum = slabs + (size_t)ns * SLAB_FLOATS;
-    float* gscale = workspace + nf_paper_bwd_workspace_floats(n_points) - 16;
-    hipStream_t s = nf_s(stream);
-    constexpr int NT = NF_MLP_NT;
-    const int64_t per_block = (int64_t)NF_MLP_WAVES * 16 * NT;
-    const int64_t grid = (n_points + per_block - 1) / per_block;
-    if (grid > 0x7fffffff) return NF_EINVAL;
     NfReduceAlt alt;
     alt.n_slices = 0;
     for (int q = 0; q < NF_REDUCE_ALT_MAX; ++q) alt.lo4[q] = alt.hi4[q] = 0;
     // the slabs are fully written by the GEMM kernel -- except, in the shared-panel plan, by the group that runs fewer slices: the
     // reduction is told which regions end early instead of a 71 MB zero-fill per call
-    if (!(!split_dw && nf_dw_reduce_alt(gset.g, NF_DW_GROUPS, ns, &alt))) {
-        alt.n_slices = 0;
-        e = hipMemsetAsync(slabs, 0, (size_t)ns * SLAB_FLOATS * sizeof(float), s);
+    bool zero_fill = true;
+    if (split_dw) nfb_dw_plan(fam.model, n_points, &pps, &ns);
+    else {
+        fam.build_groups(gset.g);
+        for (int k = 0; k <= NF_DW_MAX_GROUPS; ++k) gset.first_block[k] = 0x7fffffff;
+        ns = nf_dw_plan_groups(gset.g, fam.n_groups, n_points, gset.first_block);
+        zero_fill = !nf_dw_reduce_alt(gset.g, fam.n_groups, ns, &alt);
+        if (zero_fill) alt.n_slices = 0;
+    }
+    float* dz = workspace;
+    float* slabs = workspace + (size_t)fam.dz_per_point * n_points;
+    float* sum = slabs + (size_t)ns * fam.slab_floats;
+    float* gscale = workspace + need - 16;
+    hipStream_t s = nf_s(stream);
+    if (zero_fill) {
+        e = hipMemsetAsync(slabs, 0, (size_t)ns * fam.slab_floats * sizeof(float), s);
+        if (e != hipSuccess) return (int)e;
+    }
+    if (precision == 2) {
+        e = hipMemsetAsync(gscale, 0, 16 * sizeof(float), s);           // max |gradient| per section, filled by the chain
         if (e != hipSuccess) return (int)e;
     }
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};          // stage_ms: dX chain | weight-gradient GEMMs | reduce + unpack
     auto mark = [&](int k) {
         if (stage_ms && hipEventCreate(&ev[k]) == hipSuccess) (void)hipEventRecord(ev[k], s);
     };
-    if (packed_t_f16) {
-        e = hipMemsetAsync(gscale, 0, 16 * sizeof(float), s);           // max |gradient| per section, filled by the chain
-        if (e != hipSuccess) return (int)e;
-        mark(0);
-        const int rc2 = nfb_launch_bwd_chain_f16(packed_t_f16, saved, d_raw, n_points, dz, gscale, stream);
-        if (rc2) return rc2;
-    } else if (packed_t_bf16) {
-        mark(0);
-        const int rc2 = nfb_launch_bwd_chain_bf16(packed_t_bf16, saved, d_raw, n_points, dz, nullptr, stream);
-        if (rc2) return rc2;
-    } else {
-        mark(0);
-        hipLaunchKernelGGL((k_paper_mlp_bwd_chain_masks<NT>), dim3((unsigned)grid), dim3(64 * NF_MLP_WAVES), 0, s, packed_t, saved, d_raw,
-                           n_points, dz);
-    }
+    mark(0);
+    int rc = fam.chain[precision](packed_t, saved, d_raw, n_points, dz, precision == 2 ? gscale : nullptr, stream);
+    if (rc) return rc;
     mark(1);
     if (split_dw) {
-        const int rc3 = packed_t_f16 ? nfb_launch_dw_gemm_f16(0, dz, d_raw, saved, n_points, pps, ns, slabs, gscale, stream)
-                                     : nfb_launch_dw_gemm_bf16(0, dz, d_raw, saved, n_points, pps, ns, slabs, nullptr, stream);
-        if (rc3) return rc3;
+        rc = precision == 2 ? nfb_launch_dw_gemm_f16(fam.model, dz, d_raw, saved, n_points, pps, ns, slabs, gscale, stream)
+                            : nfb_launch_dw_gemm_bf16(fam.model, dz, d_raw, saved, n_points, pps, ns, slabs, nullptr, stream);
+        if (rc) return rc;
     } else {
-        hipLaunchKernelGGL((k_dw_gemm_lds<0>), dim3(gset.first_block[NF_DW_GROUPS]), dim3(64 * NF_DW_WAVES), 0, s, gset, (int)SLAB_FLOATS, dz, d_raw,
-                           saved_f32 ? saved_f32 : saved, n_points, slabs);
+        fam.dw_f32(gset, dz, d_raw, saved_f32 ? saved_f32 : saved, n_points, slabs, s);
     }
     mark(2);
-    hipLaunchKernelGGL((k_grad_reduce<0>), dim3(512), dim3(256), 0, s, slabs, ns, (int)SLAB_FLOATS, sum, alt);
-    NfGradOffsets offs;
-    offs.off[0] = offs.blk[0] = 0;
-    for (int i = 0; i <= NF_PAPER_NUM_PARAMS; ++i) {                  // 26 tensors, then the 32 latent-code gradients
-        const int numel = i < NF_PAPER_NUM_PARAMS ? NF_PARAM_NUMEL[i] : 32;
-        offs.off[i + 1] = offs.off[i] + numel;
-        offs.blk[i + 1] = offs.blk[i] + (numel + 255) / 256;
-    }
-    hipLaunchKernelGGL(k_paper_grad_unpack, dim3(offs.blk[NF_PAPER_NUM_PARAMS + 1]), dim3(256), 0, s, sum, packed, cond, offs, grads);
+    fam.reduce_unpack(slabs, ns, alt, sum, packed, cond, grads, s);
     if (stage_ms) {
         mark(3);
         e = hipStreamSynchronize(s);
@@ -452,6 +410,48 @@ static int nf_bwd_impl(const float* packed, const float* packed_t, const void* p
     NF_RETURN_LAUNCH();
 }
 
+// =================================================================================================
+// the paper model's record and entry points
+// =================================================================================================
+// defined in nf_mlp_bf16_bwd.hip / nf_mlp_f16_bwd.hip
+int nfb_launch_bwd_chain_bf16(const void* packed_t, const float* saved, const float* d_raw, int64_t n_points, float* dz,
+                              float* gscale, nf_stream_t stream);
+int nfb_launch_bwd_chain_f16(const void* packed_t, const float* saved, const float* d_raw, int64_t n_points, float* dz,
+                             float* gscale, nf_stream_t stream);
+
+static int nf_paper_chain_f32(const void* packed_t, const float* saved, const float* d_raw, int64_t n_points, float* dz, float*,
+                              nf_stream_t stream) {
+    const int64_t per_block = (int64_t)NF_MLP_WAVES * 16 * NF_MLP_NT;
+    hipLaunchKernelGGL((k_paper_mlp_bwd_chain_masks<NF_MLP_NT>), dim3((unsigned)((n_points + per_block - 1) / per_block)),
+                       dim3(64 * NF_MLP_WAVES), 0, nf_s(stream), (const float*)packed_t, saved, d_raw, n_points, dz);
+    return 0;
+}
+
+static void nf_paper_dw_f32(const NfDwGroupSet& gset, const float* dz, const float* d_raw, const float* saved, int64_t n_points,
+                            float* slabs, hipStream_t s) {
+    hipLaunchKernelGGL((k_dw_gemm_lds<0>), dim3(gset.first_block[NF_DW_GROUPS]), dim3(64 * NF_DW_WAVES), 0, s, gset, (int)nfl::SLAB_FLOATS,
+                       dz, d_raw, saved, n_points, slabs);
+}
+
+static void nf_paper_reduce_unpack(const float* slabs, int ns, const NfReduceAlt& alt, float* sum, const float* packed, const float* cond,
+                                   float* grads, hipStream_t s) {
+    hipLaunchKernelGGL((k_grad_reduce<0>), dim3(512), dim3(256), 0, s, slabs, ns, (int)nfl::SLAB_FLOATS, sum, alt);
+    NfGradOffsets offs;
+    offs.off[0] = offs.blk[0] = 0;
+    for (int i = 0; i <= NF_PAPER_NUM_PARAMS; ++i) {                  // 26 tensors, then the 32 latent-code gradients
+        const int numel = i < NF_PAPER_NUM_PARAMS ? NF_PARAM_NUMEL[i] : 32;
+        offs.off[i + 1] = offs.off[i] + numel;
+        offs.blk[i + 1] = offs.blk[i] + (numel + 255) / 256;
+    }
+    hipLaunchKernelGGL(k_paper_grad_unpack, dim3(offs.blk[NF_PAPER_NUM_PARAMS + 1]), dim3(256), 0, s, sum, packed, cond, offs, grads);
+}
+
+static const NfBwdFamily nf_paper_bwd = {0, nfl::DZ_PER_POINT, nfl::SLAB_FLOATS, NF_DW_GROUPS, nf_build_dw_groups,
+                                         {nf_paper_chain_f32, nfb_launch_bwd_chain_bf16, nfb_launch_bwd_chain_f16},
+                                         nf_paper_dw_f32, nf_paper_reduce_unpack};
+
+extern "C" size_t nf_paper_bwd_workspace_floats(int64_t n_points) { return nf_bwd_workspace_floats(nf_paper_bwd, n_points); }
+
 // Measurement hook (bench.py's per-kernel training roofline): one backward in arithmetic `precision` (0 exact f32, 1 split-bf16,
 // 2 split-fp16; packed_t_any = the matching transposed image / stream) with HIP events recorded on `stream` between its stages;
 // synchronises the stream and returns stage_ms[3] = {dX chain, weight-gradient GEMMs, slab reduction + unpack} in milliseconds.
@@ -459,17 +459,14 @@ extern "C" int nf_paper_mlp_bwd_stage_ms(const float* packed, const void* packed
                                          const float* d_raw, int64_t n_rays, int n_samples, float* workspace, size_t workspace_floats,
                                          float* grads, float* stage_ms, nf_stream_t stream) {
     if (!packed_t_any || !stage_ms || precision < 0 || precision > 2) return NF_EINVAL;
-    return nf_bwd_impl(packed, precision == 0 ? (const float*)packed_t_any : nullptr, precision == 1 ? packed_t_any : nullptr,
-                       precision == 2 ? packed_t_any : nullptr, precision != 0, cond, saved, d_raw, n_rays, n_samples, workspace,
-                       workspace_floats, grads, stream, stage_ms);
+    return nf_bwd_run(nf_paper_bwd, precision, packed, packed_t_any, cond, saved, d_raw, n_rays, n_samples, workspace, workspace_floats,
+                      grads, stream, stage_ms);
 }
 
 extern "C" int nf_paper_mlp_bwd(const float* packed, const float* packed_t, const float* cond, const float* saved,
                                 const float* d_raw, int64_t n_rays, int n_samples, float* workspace, size_t workspace_floats,
                                 float* grads, nf_stream_t stream) {
-    if (!packed_t) return NF_EINVAL;
-    return nf_bwd_impl(packed, packed_t, nullptr, nullptr, false, cond, saved, d_raw, n_rays, n_samples, workspace, workspace_floats, grads,
-                       stream);
+    return nf_bwd_run(nf_paper_bwd, 0, packed, packed_t, cond, saved, d_raw, n_rays, n_samples, workspace, workspace_floats, grads, stream);
 }
 
 // Same, with the dX chain (nf_mlp_bf16_bwd.hip) and, unless exact_dw, the weight-gradient GEMMs (nf_mlp_bf16_dw.hip) on the
@@ -478,9 +475,9 @@ extern "C" int nf_paper_mlp_bwd(const float* packed, const float* packed_t, cons
 extern "C" int nf_paper_mlp_bwd_bf16(const float* packed, const void* packed_t_bf16, const float* cond, const float* saved,
                                      const float* d_raw, int64_t n_rays, int n_samples, float* workspace, size_t workspace_floats,
                                      float* grads, int exact_dw, const float* saved_f32, nf_stream_t stream) {
-    if (!packed_t_bf16 || (exact_dw && !saved_f32)) return NF_EINVAL;
-    return nf_bwd_impl(packed, nullptr, packed_t_bf16, nullptr, exact_dw == 0, cond, saved, d_raw, n_rays, n_samples, workspace,
-                       workspace_floats, grads, stream, nullptr, exact_dw ? saved_f32 : nullptr);
+    if (exact_dw && !saved_f32) return NF_EINVAL;
+    return nf_bwd_run(nf_paper_bwd, 1, packed, packed_t_bf16, cond, saved, d_raw, n_rays, n_samples, workspace, workspace_floats, grads,
+                      stream, nullptr, exact_dw ? saved_f32 : nullptr);
 }
 
 // Same on fp16 operand pairs ("f16x3": fp32-class accuracy at the split-bf16 speed): dX chain (nf_mlp_f16_bwd.hip) and weight-
@@ -489,9 +486,8 @@ extern "C" int nf_paper_mlp_bwd_bf16(const float* packed, const void* packed_t_b
 extern "C" int nf_paper_mlp_bwd_f16(const float* packed, const void* packed_t_f16, const float* cond, const float* saved,
                                     const float* d_raw, int64_t n_rays, int n_samples, float* workspace, size_t workspace_floats,
                                     float* grads, nf_stream_t stream) {
-    if (!packed_t_f16) return NF_EINVAL;
-    return nf_bwd_impl(packed, nullptr, nullptr, packed_t_f16, true, cond, saved, d_raw, n_rays, n_samples, workspace, workspace_floats,
-                       grads, stream);
+    return nf_bwd_run(nf_paper_bwd, 2, packed, packed_t_f16, cond, saved, d_raw, n_rays, n_samples, workspace, workspace_floats, grads,
+                      stream);
 }
 
 // host-only self-test of the exact-f32 group table (tests/test_host.py)

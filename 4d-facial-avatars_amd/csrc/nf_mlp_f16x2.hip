@@ -31,13 +31,5 @@
 
 extern "C" int nf_paper_mlp_fwd_f16x2(const void* packed_f16, const float* cond, const float* ro, const float* rd, const float* rd_view,
                                       const float* z, int64_t n_rays, int n_samples, float* raw, nf_stream_t stream) {
-    if (n_rays == 0 && n_samples > 0) return 0;            // nothing to do (empty tensors have NULL data pointers)
-    if (!packed_f16 || !cond || !ro || !rd || !z || !raw || n_rays < 0 || n_samples <= 0) return NF_EINVAL;
-    const int64_t n_points = n_rays * n_samples;
-    if (n_points == 0) return 0;
-    const int64_t grid = (n_points + 127) / 128;
-    if (grid > 0x7fffffff) return NF_EINVAL;
-    hipLaunchKernelGGL(k_paper_mlp_fwd_f16x2, dim3((unsigned)grid), dim3(256), 0, nf_s(stream), reinterpret_cast<const char*>(packed_f16),
-                       cond, ro, rd, rd_view ? rd_view : rd, z, n_points, n_samples, raw, (float*)nullptr);
-    NF_RETURN_LAUNCH();
+    return nf_split_fwd(k_paper_mlp_fwd_f16x2, NF_FWD_INFER, packed_f16, cond, ro, rd, rd_view, z, n_rays, n_samples, raw, nullptr, stream);
 }

@@ -16,17 +16,12 @@
 
 static void nf_lcode_table(std::vector<uint32_t>& t) {
     using namespace nlc;
-    const uint32_t Z = 0xFF000000u;
-    t.assign(PACKED, Z);
-    auto code = [](int tensor, int row, int col, int ncols) { return ((uint32_t)tensor << 24) | (uint32_t)(row * ncols + col); };
+    t.assign(PACKED, NF_ZERO_CODE);
     auto fill = [&](int off, int nk, int no_tiles, int tensor, int n_out, int n_cols, auto col_of) {
-        for (int ni = 0; ni < nk; ++ni)
-            for (int no = 0; no < no_tiles; ++no)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int r = 0; r < 4; ++r) {
-                        const int g = lane >> 4, i = lane & 15, n = 16 * no + i, col = col_of(16 * ni + 4 * g + r);
-                        if (n < n_out && col >= 0) t[(size_t)off + ((size_t)(ni * no_tiles + no) * 64 + lane) * 4 + r] = code(tensor, n, col, n_cols);
-                    }
+        nf_fill_frag(t, off, nk, no_tiles, [&](int slot, int n) {
+            const int col = col_of(slot);
+            return n < n_out && col >= 0 ? nf_code(tensor, n, col, n_cols) : NF_ZERO_CODE;
+        });
     };
     auto ident = [](int s) { return s; };
     fill(OFF_L1, 4, 16, 0, 256, 171, [](int s) { return nfl::pe_slot_to_col(s); });
@@ -43,17 +38,17 @@ static void nf_lcode_table(std::vector<uint32_t>& t) {
     fill(OFF_RGB, 8, 1, 12, 3, 128, ident);
     fill(OFF_DIRE, 18, 8, 8, 128, 280, [](int s) { return s < 280 ? s : -1; });
     for (int n = 0; n < 256; ++n)
-        for (int k = 0; k < 108; ++k) t[OFF_WC1 + n * 108 + k] = code(0, n, 63 + k, 171);
+        for (int k = 0; k < 108; ++k) t[OFF_WC1 + n * 108 + k] = nf_code(0, n, 63 + k, 171);
     for (int n = 0; n < 128; ++n)
         for (int f = 0; f < 4; ++f)
             for (int sc = 0; sc < 2; ++sc)
-                for (int comp = 1; comp < 3; ++comp) t[OFF_WCD + n * 16 + 4 * f + 2 * sc + (comp - 1)] = code(8, n, 256 + 6 * f + 3 * sc + comp, 280);
+                for (int comp = 1; comp < 3; ++comp) t[OFF_WCD + n * 16 + 4 * f + 2 * sc + (comp - 1)] = nf_code(8, n, 256 + 6 * f + 3 * sc + comp, 280);
     const int b256[5] = {1, 3, 5, 7, 15};          // layer1, layers_xyz.0..2, fc_feat biases
     for (int l = 0; l < 5; ++l)
-        for (int n = 0; n < 256; ++n) t[OFF_BIAS + 256 * l + n] = code(b256[l], 0, n, 256);
-    t[OFF_BIAS + B_ALPHA] = code(11, 0, 0, 1);
-    for (int n = 0; n < 128; ++n) t[OFF_BIAS + B_DIR + n] = code(9, 0, n, 128);
-    for (int n = 0; n < 3; ++n) t[OFF_BIAS + B_RGB + n] = code(13, 0, n, 3);
+        for (int n = 0; n < 256; ++n) t[OFF_BIAS + 256 * l + n] = nf_code(b256[l], 0, n, 256);
+    t[OFF_BIAS + B_ALPHA] = nf_code(11, 0, 0, 1);
+    for (int n = 0; n < 128; ++n) t[OFF_BIAS + B_DIR + n] = nf_code(9, 0, n, 128);
+    for (int n = 0; n < 3; ++n) t[OFF_BIAS + B_RGB + n] = nf_code(13, 0, n, 3);
 }
 
 static NfPackTable g_lcode_table;
@@ -478,22 +473,18 @@ k_lcode_mlp_fwd_save(const float* __restrict__ packed, const float* __restrict__
 
 static int nf_lcode_launch_fwd(const float* packed, const float* cond, const float* ro, const float* rd, const float* rd_view,
                                const float* z, int64_t n_rays, int n_samples, float* raw, float* saved, nf_stream_t stream) {
-    if (n_rays == 0 && n_samples > 0) return 0;            // nothing to do (empty tensors have NULL data pointers)
-    if (!packed || !cond || !ro || !rd || !z || !raw || n_rays < 0 || n_samples <= 0) return NF_EINVAL;
-    const int64_t n_points = n_rays * n_samples;
-    if (n_points == 0) return 0;
     constexpr int NT = NF_MLP_NT;
-    const int64_t per_block = (int64_t)NF_MLP_WAVES * 16 * NT;
-    const int64_t grid = (n_points + per_block - 1) / per_block;
-    if (grid > 0x7fffffff) return NF_EINVAL;
-    if (saved && n_points >= ((int64_t)1 << 22)) return NF_EINVAL;       // the save path addresses a section with 32-bit byte offsets (1 KiB per point)
-    if (saved)
-        hipLaunchKernelGGL((k_lcode_mlp_fwd_save<NT>), dim3((unsigned)grid), dim3(64 * NF_MLP_WAVES), 0, nf_s(stream), packed, cond, ro,
-                           rd, rd_view ? rd_view : rd, z, n_points, n_samples, raw, saved);
-    else
-        hipLaunchKernelGGL((k_lcode_mlp_fwd<NT>), dim3((unsigned)grid), dim3(64 * NF_MLP_WAVES), 0, nf_s(stream), packed, cond, ro,
-                           rd, rd_view ? rd_view : rd, z, n_points, n_samples, raw);
-    NF_RETURN_LAUNCH();
+    static_assert(NF_MLP_WAVES * 16 * NT == 128, "nf_mlp_fwd_launch sizes the grid for 128 points per workgroup");
+    const float* rdv = rd_view ? rd_view : rd;
+    return nf_mlp_fwd_launch(saved ? NF_FWD_TRAIN_F32 : NF_FWD_INFER, packed, cond, ro, rd, z, raw, saved, n_rays, n_samples,
+                             [&](int64_t n_points, unsigned grid) {
+        if (saved)
+            hipLaunchKernelGGL((k_lcode_mlp_fwd_save<NT>), dim3(grid), dim3(64 * NF_MLP_WAVES), 0, nf_s(stream), packed, cond, ro, rd, rdv, z,
+                               n_points, n_samples, raw, saved);
+        else
+            hipLaunchKernelGGL((k_lcode_mlp_fwd<NT>), dim3(grid), dim3(64 * NF_MLP_WAVES), 0, nf_s(stream), packed, cond, ro, rd, rdv, z,
+                               n_points, n_samples, raw);
+    });
 }
 
 extern "C" int nf_lcode_mlp_fwd(const float* packed, const float* cond, const float* ro, const float* rd, const float* rd_view,

@@ -17,28 +17,26 @@
 
 static void nf_lcode_table_bf16(std::vector<uint32_t>& t) {
     using namespace nfb;
-    const uint32_t Z = 0xFF000000u;
-    t.assign((size_t)N_PAIRS * 512, Z);
-    auto code = [](int tensor, int row, int col, int ncols) { return ((uint32_t)tensor << 24) | (uint32_t)(row * ncols + col); };
+    t.assign((size_t)N_PAIRS * 512, NF_ZERO_CODE);
     for (int l = 0; l < NL; ++l)
         for (int s = 0; s < KS[l]; ++s)
             for (int nt = 0; nt < NO[l]; ++nt)
                 for (int lane = 0; lane < 64; ++lane)
                     for (int j = 0; j < 8; ++j) {
                         const int h = lane >> 5, i = lane & 31, n = 32 * nt + i;
-                        uint32_t c = Z;
+                        uint32_t c = NF_ZERO_CODE;
                         switch (l) {
-                            case 0: { const int col = pe_col(s, h, j); if (col >= 0) c = code(0, n, col, 171); } break;
-                            case 1: c = code(2, n, hid_feature(s, h, j), 256); break;
-                            case 2: c = code(4, n, hid_feature(s, h, j), 256); break;
-                            case 3: c = code(6, n, hid_feature(s, h, j), 256); break;
-                            case 4: if (n == 0) c = code(10, 0, hid_feature(s, h, j), 256); break;
-                            case 5: c = code(14, n, hid_feature(s, h, j), 256); break;
+                            case 0: { const int col = pe_col(s, h, j); if (col >= 0) c = nf_code(0, n, col, 171); } break;
+                            case 1: c = nf_code(2, n, hid_feature(s, h, j), 256); break;
+                            case 2: c = nf_code(4, n, hid_feature(s, h, j), 256); break;
+                            case 3: c = nf_code(6, n, hid_feature(s, h, j), 256); break;
+                            case 4: if (n == 0) c = nf_code(10, 0, hid_feature(s, h, j), 256); break;
+                            case 5: c = nf_code(14, n, hid_feature(s, h, j), 256); break;
                             case 6:
-                                if (s < 16) c = code(8, n, hid_feature(s, h, j), 280);
-                                else if (s == 16) { const int col = dir_col(h, j); if (col >= 0) c = code(8, n, col, 280); }
+                                if (s < 16) c = nf_code(8, n, hid_feature(s, h, j), 280);
+                                else if (s == 16) { const int col = dir_col(h, j); if (col >= 0) c = nf_code(8, n, col, 280); }
                                 break;
-                            case 7: if (n < 3) c = code(12, n, hid_feature(s, h, j), 128); break;
+                            case 7: if (n < 3) c = nf_code(12, n, hid_feature(s, h, j), 128); break;
                         }
                         t[((size_t)(pair_off(l) + s * NO[l] + nt)) * 512 + lane * 8 + j] = c;
                     }
@@ -61,24 +59,9 @@ extern "C" int nf_lcode_pack_bf16(const float* const* params, void* stream_out, 
 // cond must be the padded table nf_lcode_condition fills (nf_lcode_cond_floats() floats >= 10 KiB)
 extern "C" int nf_lcode_mlp_fwd_bf16(const void* packed_bf16, const float* cond, const float* ro, const float* rd, const float* rd_view,
                                      const float* z, int64_t n_rays, int n_samples, float* raw, nf_stream_t stream) {
-    if (n_rays == 0 && n_samples > 0) return 0;            // nothing to do (empty tensors have NULL data pointers)
-    if (!packed_bf16 || !cond || !ro || !rd || !z || !raw || n_rays < 0 || n_samples <= 0) return NF_EINVAL;
-    const int64_t n_points = n_rays * n_samples;
-    if (n_points == 0) return 0;
-    const int64_t grid = (n_points + 127) / 128;
-    if (grid > 0x7fffffff) return NF_EINVAL;
-    hipLaunchKernelGGL(k_lcode_mlp_fwd_bf16, dim3((unsigned)grid), dim3(256), 0, nf_s(stream), reinterpret_cast<const char*>(packed_bf16),
-                       cond, ro, rd, rd_view ? rd_view : rd, z, n_points, n_samples, raw, (float*)nullptr);
-    NF_RETURN_LAUNCH();
+    return nf_split_fwd(k_lcode_mlp_fwd_bf16, NF_FWD_INFER, packed_bf16, cond, ro, rd, rd_view, z, n_rays, n_samples, raw, nullptr, stream);
 }
 
 // host-only: the gather table of this stream (one 32-bit code per bf16 element of the hi blocks: tensor id << 24 | element
 // offset, 0xFF000000 = zero) for tests/test_host.py; out == NULL returns the number of entries.  Forward stream of the second model family.
-extern "C" long nf_lcode_stream_table_bf16(uint32_t* out, size_t n_entries) {
-    std::vector<uint32_t> t;
-    nf_lcode_table_bf16(t);
-    if (!out) return (long)t.size();
-    if (n_entries != t.size()) return -1;
-    for (size_t i = 0; i < t.size(); ++i) out[i] = t[i];
-    return (long)t.size();
-}
+extern "C" long nf_lcode_stream_table_bf16(uint32_t* out, size_t n_entries) { return nf_export_table(nf_lcode_table_bf16, out, n_entries); }

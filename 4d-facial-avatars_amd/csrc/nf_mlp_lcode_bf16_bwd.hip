@@ -6,29 +6,18 @@
 //   3 layers_xyz.2^T   4 layers_xyz.1^T   5 layers_xyz.0^T (-> dZ of layer1, which has no activation)
 #include <vector>
 #include <mutex>
-#include "nf_common.h"
+#include "nf_mlp_split_common.h"
 #include "nf_mlp_lcode_layout.h"
 
 // NFB_F16 = 1 (nf_mlp_lcode_f16_bwd.hip includes this file): the same chain on fp16 operand pairs, see nf_mlp_bf16_bwd.hip
-#ifndef NFB_F16
-#define NFB_F16 0
-#endif
 #if NFB_F16
-typedef _Float16 nfb_elt;
-typedef _Float16 bf16x8 __attribute__((ext_vector_type(8)));
-#define NFB_MFMA __builtin_amdgcn_mfma_f32_32x32x16_f16
 #define NFB_BWD_NAME(x) x##_f16
 #ifndef NFB_TILE_GROUP
 #define NFB_TILE_GROUP 4
 #endif
 #else
-typedef __bf16 nfb_elt;
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-#define NFB_MFMA __builtin_amdgcn_mfma_f32_32x32x16_bf16
 #define NFB_BWD_NAME(x) x##_bf16
 #endif
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 namespace nfb {
@@ -38,7 +27,6 @@ constexpr int NO[NL] = {4, 8, 8, 8, 8, 8};
 constexpr int pair_off(int l) { int o = 0; for (int i = 0; i < l; ++i) o += KS[i] * NO[i]; return o; }
 constexpr int N_PAIRS = pair_off(NL);
 constexpr int STREAM_BF16 = N_PAIRS * 2 * 512;
-__host__ __device__ constexpr int hid_feature(int s, int h, int j) { return 16 * s + 4 * h + (j & 3) + 8 * (j >> 2); }
 }  // namespace nfb
 
 #include "nf_mlp_bf16_machinery.inc"
@@ -50,26 +38,24 @@ __host__ __device__ constexpr int hid_feature(int s, int h, int j) { return 16 *
 
 static void nf_lcode_table_bf16_t(std::vector<uint32_t>& t) {
     using namespace nfb;
-    const uint32_t Z = 0xFF000000u;
-    t.assign((size_t)N_PAIRS * 512, Z);
-    auto code = [](int tensor, int row, int col, int ncols) { return ((uint32_t)tensor << 24) | (uint32_t)(row * ncols + col); };
+    t.assign((size_t)N_PAIRS * 512, NF_ZERO_CODE);
     for (int l = 0; l < NL; ++l)
         for (int s = 0; s < KS[l]; ++s)
             for (int nt = 0; nt < NO[l]; ++nt)
                 for (int lane = 0; lane < 64; ++lane)
                     for (int j = 0; j < 8; ++j) {
                         const int h = lane >> 5, i = lane & 31, col = 32 * nt + i, row = hid_feature(s, h, j);
-                        uint32_t c = Z;
+                        uint32_t c = NF_ZERO_CODE;
                         switch (l) {
-                            case 0: if (s == 0 && h == 0 && j < 3) c = code(12, j, col, 128); break;      // slots 0..2 carry d r, d g, d b
-                            case 1: if (row < 128) c = code(8, row, col, 280); break;
+                            case 0: if (s == 0 && h == 0 && j < 3) c = nf_code(12, j, col, 128); break;      // slots 0..2 carry d r, d g, d b
+                            case 1: if (row < 128) c = nf_code(8, row, col, 280); break;
                             case 2:                                                                      // k-step 16, slot (0, 0): d sigma
-                                if (s < 16) c = code(14, row, col, 256);
-                                else if (s == 16 && h == 0 && j == 0) c = code(10, 0, col, 256);
+                                if (s < 16) c = nf_code(14, row, col, 256);
+                                else if (s == 16 && h == 0 && j == 0) c = nf_code(10, 0, col, 256);
                                 break;
-                            case 3: c = code(6, row, col, 256); break;
-                            case 4: c = code(4, row, col, 256); break;
-                            case 5: c = code(2, row, col, 256); break;
+                            case 3: c = nf_code(6, row, col, 256); break;
+                            case 4: c = nf_code(4, row, col, 256); break;
+                            case 5: c = nf_code(2, row, col, 256); break;
                         }
                         t[((size_t)(pair_off(l) + s * NO[l] + nt)) * 512 + lane * 8 + j] = c;
                     }
@@ -259,12 +245,5 @@ int NFB_BWD_NAME(nfb_lcode_launch_bwd_chain)(const void* packed_t, const float* 
 #if !NFB_F16
 // host-only: the gather table of this stream (one 32-bit code per bf16 element of the hi blocks: tensor id << 24 | element
 // offset, 0xFF000000 = zero) for tests/test_host.py; out == NULL returns the number of entries.  Transposed stream of the second model family.
-extern "C" long nf_lcode_stream_table_bwd_bf16(uint32_t* out, size_t n_entries) {
-    std::vector<uint32_t> t;
-    nf_lcode_table_bf16_t(t);
-    if (!out) return (long)t.size();
-    if (n_entries != t.size()) return -1;
-    for (size_t i = 0; i < t.size(); ++i) out[i] = t[i];
-    return (long)t.size();
-}
+extern "C" long nf_lcode_stream_table_bwd_bf16(uint32_t* out, size_t n_entries) { return nf_export_table(nf_lcode_table_bf16_t, out, n_entries); }
 #endif

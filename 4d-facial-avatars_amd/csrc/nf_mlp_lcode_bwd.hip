@@ -11,7 +11,7 @@
 #include "nf_mlp_dev.h"
 #include "nf_mlp_stream.h"
 #include "nf_mlp_lcode_layout.h"
-#include "nf_mlp_dw.h"
+#include "nf_mlp_bwd.h"
 #include "nf_pack.h"
 
 
@@ -20,17 +20,8 @@
 // =================================================================================================
 static void nf_lcode_table_t(std::vector<uint32_t>& t) {
     using namespace nlc;
-    const uint32_t Z = 0xFF000000u;
-    t.assign(PACKED_T, Z);
-    auto fill = [&](int off, int nk, int no_tiles, int tensor, int n_rows, int n_cols) {
-        for (int ni = 0; ni < nk; ++ni)
-            for (int no = 0; no < no_tiles; ++no)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int r = 0; r < 4; ++r) {
-                        const int g = lane >> 4, i = lane & 15, row = 16 * ni + 4 * g + r, col = 16 * no + i;
-                        if (row < n_rows) t[(size_t)off + ((size_t)(ni * no_tiles + no) * 64 + lane) * 4 + r] = ((uint32_t)tensor << 24) | (uint32_t)(row * n_cols + col);
-                    }
-    };
+    t.assign(PACKED_T, NF_ZERO_CODE);
+    auto fill = [&](int off, int nk, int no_tiles, int tensor, int n_rows, int n_cols) { nf_fill_frag_t(t, off, nk, no_tiles, tensor, n_rows, n_cols); };
     fill(OFFT_RGB, 1, 8, 12, 3, 128);                       // fc_rgb.weight (3, 128)
     fill(OFFT_DIR, 8, 16, 8, 128, 280);                     // layers_dir.0.weight[:, :256]
     fill(OFFT_FEAT, 16, 16, 14, 256, 256);                  // fc_feat.weight
@@ -274,101 +265,46 @@ static const int NF_LC_PARAM_NUMEL[nlc::NPARAMS] = {256 * 171, 256, 65536, 256, 
 
 extern "C" size_t nf_lcode_grad_floats(void) { return (size_t)nlc::GRAD_FLOATS; }
 
-// defined in nf_mlp_bf16_dw.hip / nf_mlp_lcode_bf16_bwd.hip
-void nfb_dw_plan(int model, int64_t n_points, int64_t* pts_per_slice, int* n_slices);
-int nfb_launch_dw_gemm_bf16(int model, const float* dz, const float* d_raw, const float* saved, int64_t n_points, int64_t pts_per_slice,
-                            int n_slices, float* slabs, const float* gscale, nf_stream_t stream);
-int nfb_launch_dw_gemm_f16(int model, const float* dz, const float* d_raw, const float* saved, int64_t n_points, int64_t pts_per_slice,
-                           int n_slices, float* slabs, const float* gscale, nf_stream_t stream);
+// defined in nf_mlp_lcode_bf16_bwd.hip / nf_mlp_lcode_f16_bwd.hip
 int nfb_lcode_launch_bwd_chain_bf16(const void* packed_t, const float* saved, const float* d_raw, int64_t n_points, float* dz,
                                     float* gscale, nf_stream_t stream);
 int nfb_lcode_launch_bwd_chain_f16(const void* packed_t, const float* saved, const float* d_raw, int64_t n_points, float* dz,
                                    float* gscale, nf_stream_t stream);
 
-extern "C" size_t nf_lcode_bwd_workspace_floats(int64_t n_points) {
-    int64_t pps; int ns, ns_b;
-    nfb_dw_plan(1, n_points, &pps, &ns);
-    NfDwGroup groups[NF_LC_DW_GROUPS];
-    nf_lcode_build_dw_groups(groups);
-    ns_b = nf_dw_plan_groups(groups, NF_LC_DW_GROUPS, n_points);
-    if (ns_b > ns) ns = ns_b;
-    return (size_t)nlc::DZ_PER_POINT * (size_t)n_points + (size_t)(ns + 1) * nlc::SLAB_FLOATS + 16;      // + max |gradient| per dz section (fp16 kernels)
+static int nf_lcode_chain_f32(const void* packed_t, const float* saved, const float* d_raw, int64_t n_points, float* dz, float*,
+                              nf_stream_t stream) {
+    const int64_t per_block = (int64_t)NF_MLP_WAVES * 16 * NF_MLP_NT;
+    hipLaunchKernelGGL((k_lcode_mlp_bwd_chain<NF_MLP_NT>), dim3((unsigned)((n_points + per_block - 1) / per_block)), dim3(64 * NF_MLP_WAVES),
+                       0, nf_s(stream), (const float*)packed_t, saved, d_raw, n_points, dz);
+    return 0;
 }
 
+static void nf_lcode_dw_f32(const NfDwGroupSet& gset, const float* dz, const float* d_raw, const float* saved, int64_t n_points,
+                            float* slabs, hipStream_t s) {
+    hipLaunchKernelGGL((k_dw_gemm_lds<1>), dim3(gset.first_block[NF_LC_DW_GROUPS]), dim3(64 * NF_DW_WAVES), 0, s, gset, (int)nlc::SLAB_FLOATS,
+                       dz, d_raw, saved, n_points, slabs);
+}
 
 // grads: nf_lcode_grad_floats() floats = the 16 tensors in nerf.models.LCODE_KEYS order, flattened, then d latent (32)
-// packed_t (exact f32) | packed_t_bf16 (split-bf16) | packed_t_f16 (split-fp16): exactly one non-NULL
-static int nf_lcode_bwd_impl(const float* packed, const float* packed_t, const void* packed_t_bf16, const void* packed_t_f16,
-                             const float* cond, const float* saved, const float* d_raw, int64_t n_rays, int n_samples, float* workspace,
-                             size_t workspace_floats, float* grads, nf_stream_t stream) {
-    using namespace nlc;
-    if (!packed || (!packed_t && !packed_t_bf16 && !packed_t_f16) || !cond || !saved || !d_raw || !workspace || !grads || n_rays <= 0 ||
-        n_samples <= 0)
-        return NF_EINVAL;
-    const bool split = packed_t_bf16 != nullptr || packed_t_f16 != nullptr;
-    const int64_t n_points = n_rays * n_samples;
-    if (workspace_floats < nf_lcode_bwd_workspace_floats(n_points)) return NF_EINVAL;
-    if (((n_points + 31) & ~(int64_t)31) >= ((int64_t)1 << 22)) return NF_EINVAL;   // 32-bit byte offsets into a (32-padded) dZ / saved section
-    int64_t pps; int ns;
-    NfDwGroupSet gset;
-    NfReduceAlt alt;
-    alt.n_slices = 0;
-    for (int q = 0; q < NF_REDUCE_ALT_MAX; ++q) alt.lo4[q] = alt.hi4[q] = 0;
-    bool zero_fill = true;
-    if (split) nfb_dw_plan(1, n_points, &pps, &ns);
-    else {
-        nf_lcode_build_dw_groups(gset.g);
-        for (int k = 0; k <= NF_DW_MAX_GROUPS; ++k) gset.first_block[k] = 0x7fffffff;
-        ns = nf_dw_plan_groups(gset.g, NF_LC_DW_GROUPS, n_points, gset.first_block);
-        pps = 0;
-        zero_fill = !nf_dw_reduce_alt(gset.g, NF_LC_DW_GROUPS, ns, &alt);   // every group writes every slab: nothing to clear
-        if (zero_fill) alt.n_slices = 0;
-    }
-    float* dz = workspace;
-    float* slabs = workspace + (size_t)DZ_PER_POINT * n_points;
-    float* sum = slabs + (size_t)ns * SLAB_FLOATS;
-    float* gscale = workspace + nf_lcode_bwd_workspace_floats(n_points) - 16;
-    hipStream_t s = nf_s(stream);
-    constexpr int NT = NF_MLP_NT;
-    const int64_t per_block = (int64_t)NF_MLP_WAVES * 16 * NT;
-    const int64_t grid = (n_points + per_block - 1) / per_block;
-    if (grid > 0x7fffffff) return NF_EINVAL;
-    hipError_t e = hipSuccess;
-    if (zero_fill) {
-        e = hipMemsetAsync(slabs, 0, (size_t)ns * SLAB_FLOATS * sizeof(float), s);
-        if (e != hipSuccess) return (int)e;
-    }
-    if (packed_t_f16) {
-        e = hipMemsetAsync(gscale, 0, 16 * sizeof(float), s);           // max |gradient| per section, filled by the chain
-        if (e != hipSuccess) return (int)e;
-        int rc = nfb_lcode_launch_bwd_chain_f16(packed_t_f16, saved, d_raw, n_points, dz, gscale, stream);
-        if (rc) return rc;
-        rc = nfb_launch_dw_gemm_f16(1, dz, d_raw, saved, n_points, pps, ns, slabs, gscale, stream);
-        if (rc) return rc;
-    } else if (split) {
-        int rc = nfb_lcode_launch_bwd_chain_bf16(packed_t_bf16, saved, d_raw, n_points, dz, nullptr, stream);
-        if (rc) return rc;
-        rc = nfb_launch_dw_gemm_bf16(1, dz, d_raw, saved, n_points, pps, ns, slabs, nullptr, stream);
-        if (rc) return rc;
-    } else {
-        hipLaunchKernelGGL((k_lcode_mlp_bwd_chain<NT>), dim3((unsigned)grid), dim3(64 * NF_MLP_WAVES), 0, s, packed_t, saved, d_raw, n_points, dz);
-        hipLaunchKernelGGL((k_dw_gemm_lds<1>), dim3(gset.first_block[NF_LC_DW_GROUPS]), dim3(64 * NF_DW_WAVES), 0, s, gset, (int)SLAB_FLOATS, dz,
-                           d_raw, saved, n_points, slabs);
-    }
-    hipLaunchKernelGGL((k_grad_reduce<1>), dim3(512), dim3(256), 0, s, slabs, ns, (int)SLAB_FLOATS, sum, alt);
+static void nf_lcode_reduce_unpack(const float* slabs, int ns, const NfReduceAlt& alt, float* sum, const float* packed, const float* cond,
+                                   float* grads, hipStream_t s) {
+    hipLaunchKernelGGL((k_grad_reduce<1>), dim3(512), dim3(256), 0, s, slabs, ns, (int)nlc::SLAB_FLOATS, sum, alt);
     NfLcodeGradOffsets offs;
     offs.off[0] = 0;
-    for (int i = 0; i < NPARAMS; ++i) offs.off[i + 1] = offs.off[i] + NF_LC_PARAM_NUMEL[i];
+    for (int i = 0; i < nlc::NPARAMS; ++i) offs.off[i + 1] = offs.off[i] + NF_LC_PARAM_NUMEL[i];
     hipLaunchKernelGGL(k_lcode_grad_unpack, dim3(1024 + 1), dim3(256), 0, s, sum, packed, cond, offs, grads);      // + 1: the d-latent workgroup
-    NF_RETURN_LAUNCH();
 }
+
+static const NfBwdFamily nf_lcode_bwd = {1, nlc::DZ_PER_POINT, nlc::SLAB_FLOATS, NF_LC_DW_GROUPS, nf_lcode_build_dw_groups,
+                                         {nf_lcode_chain_f32, nfb_lcode_launch_bwd_chain_bf16, nfb_lcode_launch_bwd_chain_f16},
+                                         nf_lcode_dw_f32, nf_lcode_reduce_unpack};
+
+extern "C" size_t nf_lcode_bwd_workspace_floats(int64_t n_points) { return nf_bwd_workspace_floats(nf_lcode_bwd, n_points); }
 
 extern "C" int nf_lcode_mlp_bwd(const float* packed, const float* packed_t, const float* cond, const float* saved, const float* d_raw,
                                 int64_t n_rays, int n_samples, float* workspace, size_t workspace_floats, float* grads,
                                 nf_stream_t stream) {
-    if (!packed_t) return NF_EINVAL;
-    return nf_lcode_bwd_impl(packed, packed_t, nullptr, nullptr, cond, saved, d_raw, n_rays, n_samples, workspace, workspace_floats, grads,
-                             stream);
+    return nf_bwd_run(nf_lcode_bwd, 0, packed, packed_t, cond, saved, d_raw, n_rays, n_samples, workspace, workspace_floats, grads, stream);
 }
 
 // Same on the split-bf16 kernels (dX chain nf_mlp_lcode_bf16_bwd.hip, weight-gradient GEMMs nf_mlp_bf16_dw.hip); `saved` must come
@@ -376,18 +312,16 @@ extern "C" int nf_lcode_mlp_bwd(const float* packed, const float* packed_t, cons
 extern "C" int nf_lcode_mlp_bwd_bf16(const float* packed, const void* packed_t_bf16, const float* cond, const float* saved,
                                      const float* d_raw, int64_t n_rays, int n_samples, float* workspace, size_t workspace_floats,
                                      float* grads, nf_stream_t stream) {
-    if (!packed_t_bf16) return NF_EINVAL;
-    return nf_lcode_bwd_impl(packed, nullptr, packed_t_bf16, nullptr, cond, saved, d_raw, n_rays, n_samples, workspace, workspace_floats,
-                             grads, stream);
+    return nf_bwd_run(nf_lcode_bwd, 1, packed, packed_t_bf16, cond, saved, d_raw, n_rays, n_samples, workspace, workspace_floats, grads,
+                      stream);
 }
 
 // Same on fp16 operand pairs ("f16x3"): `saved` from nf_lcode_mlp_fwd_train_f16, packed_t_f16 from nf_lcode_pack_bwd_f16.
 extern "C" int nf_lcode_mlp_bwd_f16(const float* packed, const void* packed_t_f16, const float* cond, const float* saved,
                                     const float* d_raw, int64_t n_rays, int n_samples, float* workspace, size_t workspace_floats,
                                     float* grads, nf_stream_t stream) {
-    if (!packed_t_f16) return NF_EINVAL;
-    return nf_lcode_bwd_impl(packed, nullptr, nullptr, packed_t_f16, cond, saved, d_raw, n_rays, n_samples, workspace, workspace_floats,
-                             grads, stream);
+    return nf_bwd_run(nf_lcode_bwd, 2, packed, packed_t_f16, cond, saved, d_raw, n_rays, n_samples, workspace, workspace_floats, grads,
+                      stream);
 }
 
 // host-only self-test of this family's exact-f32 group table (tests/test_host.py)

@@ -13,9 +13,8 @@
 #define NFB_KERNEL_NAME k_lcode_mlp_fwd_f16_train
 #include "nf_mlp_lcode_bf16_kernel.inc"
 
-int nfh_lcode_launch_train(const char* wstream, const float* cond, const float* ro, const float* rd, const float* rd_view, const float* z,
-                           int64_t n_points, int n_samples, float* raw, float* saved, unsigned grid, nf_stream_t stream) {
-    hipLaunchKernelGGL(k_lcode_mlp_fwd_f16_train, dim3(grid), dim3(256), 0, nf_s(stream), wstream, cond, ro, rd, rd_view, z, n_points,
-                       n_samples, raw, saved);
-    NF_RETURN_LAUNCH();
+extern "C" int nf_lcode_mlp_fwd_train_f16(const void* packed_f16, const float* cond, const float* ro, const float* rd, const float* rd_view,
+                                          const float* z, int64_t n_rays, int n_samples, float* raw, float* saved, nf_stream_t stream) {
+    return nf_split_fwd(k_lcode_mlp_fwd_f16_train, NF_FWD_TRAIN_SPLIT, packed_f16, cond, ro, rd, rd_view, z, n_rays, n_samples, raw, saved,
+                        stream);
 }

@@ -7,6 +7,39 @@
 #include <mutex>
 #include "nf_common.h"
 
+// ---- gather-table codes (host) ----
+static const uint32_t NF_ZERO_CODE = 0xFF000000u;
+static inline uint32_t nf_code(int tensor, int row, int col, int ncols) { return ((uint32_t)tensor << 24) | (uint32_t)(row * ncols + col); }
+
+// One layer section of an exact-f32 fragment image: block (ni, no), lane (g = lane >> 4, i = lane & 15), r holds the element at
+// k index 16 ni + 4 g + r and n index 16 no + i; code(k, n) names it (NF_ZERO_CODE: leave the entry as it is).
+template <class Code>
+static void nf_fill_frag(std::vector<uint32_t>& t, int off, int nk, int no_tiles, Code code) {
+    for (int ni = 0; ni < nk; ++ni)
+        for (int no = 0; no < no_tiles; ++no)
+            for (int lane = 0; lane < 64; ++lane)
+                for (int r = 0; r < 4; ++r) {
+                    const uint32_t c = code(16 * ni + 4 * (lane >> 4) + r, 16 * no + (lane & 15));
+                    if (c != NF_ZERO_CODE) t[(size_t)off + ((size_t)(ni * no_tiles + no) * 64 + lane) * 4 + r] = c;
+                }
+}
+
+// Transposed section (A operand of the backward products): row = k index, column = col0 + n index of W (n_rows x n_cols)
+static inline void nf_fill_frag_t(std::vector<uint32_t>& t, int off, int nk, int no_tiles, int tensor, int n_rows, int n_cols, int col0 = 0) {
+    nf_fill_frag(t, off, nk, no_tiles, [&](int row, int n) { return row < n_rows ? nf_code(tensor, row, col0 + n, n_cols) : NF_ZERO_CODE; });
+}
+
+// Host-only export of a gather table for tests/test_host.py: out == NULL returns the number of entries, a wrong n_entries -1.
+template <class Build>
+static long nf_export_table(Build build, uint32_t* out, size_t n_entries) {
+    std::vector<uint32_t> t;
+    build(t);
+    if (!out) return (long)t.size();
+    if (n_entries != t.size()) return -1;
+    for (size_t i = 0; i < t.size(); ++i) out[i] = t[i];
+    return (long)t.size();
+}
+
 template <int N>
 struct NfPackPtrs { const float* p[N]; };
 

@@ -24,18 +24,12 @@ constexpr int SAVED_PER_POINT = 320;
 
 static void nf_tiny_table(std::vector<uint32_t>& t) {
     using namespace nft;
-    const uint32_t Z = 0xFF000000u;
-    t.assign(PACKED, Z);
+    t.assign(PACKED, NF_ZERO_CODE);
     auto fill = [&](int off, int nk, int no_tiles, int tensor, int n_out, int n_cols, bool pe) {
-        for (int ni = 0; ni < nk; ++ni)
-            for (int no = 0; no < no_tiles; ++no)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int r = 0; r < 4; ++r) {
-                        const int g = lane >> 4, i = lane & 15, n = 16 * no + i, slot = 16 * ni + 4 * g + r;
-                        const int col = pe ? nfl::pe_slot_to_col(slot) : slot;
-                        if (n < n_out && col >= 0)
-                            t[(size_t)off + ((size_t)(ni * no_tiles + no) * 64 + lane) * 4 + r] = ((uint32_t)tensor << 24) | (uint32_t)(n * n_cols + col);
-                    }
+        nf_fill_frag(t, off, nk, no_tiles, [&](int slot, int n) {
+            const int col = pe ? nfl::pe_slot_to_col(slot) : slot;
+            return n < n_out && col >= 0 ? nf_code(tensor, n, col, n_cols) : NF_ZERO_CODE;
+        });
     };
     fill(OFF_1, 4, 8, 0, 128, 63, true);
     fill(OFF_2, 8, 8, 2, 128, 128, false);
@@ -187,16 +181,8 @@ constexpr int N_JOBS = 3;
 // block (ni, no), lane (g, i), r  ->  W[row = 16 ni + 4 g + r][16 no + i]   (A operand of the transposed product)
 static void nf_tiny_table_t(std::vector<uint32_t>& t) {
     using namespace nft;
-    t.assign(PACKED_T, 0xFF000000u);
-    auto fill = [&](int off, int nk, int no_tiles, int tensor, int n_rows, int n_cols) {
-        for (int ni = 0; ni < nk; ++ni)
-            for (int no = 0; no < no_tiles; ++no)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int r = 0; r < 4; ++r) {
-                        const int g = lane >> 4, i = lane & 15, row = 16 * ni + 4 * g + r, col = 16 * no + i;
-                        if (row < n_rows) t[(size_t)off + ((size_t)(ni * no_tiles + no) * 64 + lane) * 4 + r] = ((uint32_t)tensor << 24) | (uint32_t)(row * n_cols + col);
-                    }
-    };
+    t.assign(PACKED_T, NF_ZERO_CODE);
+    auto fill = [&](int off, int nk, int no_tiles, int tensor, int n_rows, int n_cols) { nf_fill_frag_t(t, off, nk, no_tiles, tensor, n_rows, n_cols); };
     fill(OFFT_3, 1, 8, 4, 4, 128);                // layer3.weight (4, 128)
     fill(OFFT_2, 8, 8, 2, 128, 128);              // layer2.weight (128, 128)
 }

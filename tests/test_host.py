@@ -444,6 +444,47 @@ def test_entry_points_reject_bad_arguments_before_touching_the_device(hip_lib):
     one = ctypes.c_void_p(16)                                                             # any non-NULL pointer: the size check comes before a launch
     assert lib.nf_flex_mlp_fwd_train(4, one, one, one, one, 1, 1 << 20, 4, one, one, None) == EINVAL      # 2^22 points: past the 32-bit section offsets
     assert lib.nf_tiny_mlp_fwd_train(one, one, one, one, 1, 1 << 20, 4, one, one, None) == EINVAL
+    # the fused MLPs of both families, every precision.  Forward: (packed, cond, ro, rd, rd_view, z, n_rays, n_samples, raw[, saved], stream)
+    for fam in ("paper", "lcode"):
+        for prec in ("", "_bf16", "_f16", "_f16x2"):
+            fwd = getattr(lib, f"nf_{fam}_mlp_fwd{prec}")
+            assert fwd(None, None, None, None, None, None, 0, 64, None, None) == 0, (fam, prec)                 # empty work
+            assert fwd(None, one, one, one, None, one, 4, 64, one, None) == EINVAL, (fam, prec)               # NULL weights
+            assert fwd(one, one, one, one, None, one, 4, 64, None, None) == EINVAL, (fam, prec)               # NULL output
+            assert fwd(one, one, one, one, None, one, -1, 64, one, None) == EINVAL, (fam, prec)
+            assert fwd(one, one, one, one, None, one, 4, 0, one, None) == EINVAL, (fam, prec)
+        # training forward: the exact-f32 save layout bounds n_points at 2^22, the split one n_points padded to 32
+        for prec, first_refused in (("", 1 << 22), ("_bf16", (1 << 22) - 31), ("_f16", (1 << 22) - 31)):
+            fwd = getattr(lib, f"nf_{fam}_mlp_fwd_train{prec}")
+            assert fwd(one, one, one, one, None, one, 0, 64, one, one, None) == 0, (fam, prec)
+            assert fwd(one, one, one, one, None, one, 4, 64, one, None, None) == EINVAL, (fam, prec)          # NULL saved
+            assert fwd(None, one, one, one, None, one, 4, 64, one, one, None) == EINVAL, (fam, prec)
+            assert fwd(one, one, one, one, None, one, first_refused, 1, one, one, None) == EINVAL, (fam, prec)
+            assert fwd(one, one, one, one, None, one, 1, first_refused, one, one, None) == EINVAL, (fam, prec)
+            # empty work with a NULL `saved`: these entry points check `saved` first
+            want = EINVAL if (fam, prec) in (("paper", ""), ("paper", "_bf16"), ("lcode", "")) else 0
+            assert fwd(None, None, None, None, None, None, 0, 64, None, None, None) == want, (fam, prec)
+        # backward: (packed, packed_t, cond, saved, d_raw, n_rays, n_samples, workspace, workspace_floats, grads[, ...], stream)
+        big = (1 << 64) - 1                                                            # any workspace passes the size check
+        for prec in ("", "_bf16", "_f16"):
+            bwd = getattr(lib, f"nf_{fam}_mlp_bwd{prec}")
+            extra = (0, None) if (fam, prec) == ("paper", "_bf16") else ()              # exact_dw, saved_f32
+            call = lambda pk, n_rays, n_samples, ws: bwd(pk, one, one, one, one, n_rays, n_samples, one, ws, one, *extra, None)
+            assert call(one, 0, 64, big) == EINVAL, (fam, prec)                           # no rays: refused, not empty
+            assert call(one, -1, 64, big) == EINVAL, (fam, prec)
+            assert call(one, 4, 0, big) == EINVAL, (fam, prec)
+            assert call(None, 4, 64, big) == EINVAL, (fam, prec)
+            assert call(one, 4, 64, 0) == EINVAL, (fam, prec)                             # workspace too small
+            assert call(one, (1 << 22) - 31, 1, big) == EINVAL, (fam, prec)               # 32-padded sections past 32-bit offsets
+            assert bwd(one, None, one, one, one, 4, 64, one, big, one, *extra, None) == EINVAL, (fam, prec)
+    assert lib.nf_paper_mlp_bwd_bf16(one, one, one, one, one, 4, 64, one, big, one, 1, None, None) == EINVAL       # exact_dw needs saved_f32
+    for precision in (-1, 3):
+        assert lib.nf_paper_mlp_bwd_stage_ms(one, one, precision, one, one, one, 4, 64, one, big, one, one, None) == EINVAL
+    assert lib.nf_paper_mlp_bwd_stage_ms(one, one, 0, one, one, one, 0, 64, one, big, one, one, None) == EINVAL
+    # the second family's backward workspace (the 256-CU slice plan of a host without a device), as sized before the shared driver
+    for n, floats in ((1, 643248), (512, 1683648), (4095, 11221280), (131072, 198348608), (259969, 379835584), (262144, 382897984)):
+        assert lib.nf_lcode_bwd_workspace_floats(n) == floats, n
+    assert lib.nf_paper_bwd_workspace_floats(262144) == 585984384
 
 
 def test_launcher_host_helpers():
