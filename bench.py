@@ -3,6 +3,7 @@
 
     python bench.py --gpus N --steps K --warmup W          (N>1: launched by torch.distributed.run)
     python bench.py ... --dump-outputs DIR                 (also: the last timed step's outputs as DIR/<name>.npy, seeded inputs)
+    python bench.py ... --full                             (also: everything else the line can carry, listed below)
 
 One *step* = one full 512x512 frame through the product path exactly as eval_transformed_rays.py drives it:
 `get_ray_bundle` + `run_one_iter_of_nerf(mode="validation")` with the shipped validation settings (64 coarse + 128 fine
@@ -14,7 +15,10 @@ exact-f32 MFMA kernels -- the reference's arithmetic (fp32 everywhere, nerf/mode
 N > 1: frames are sharded over ranks (eval is embarrassingly parallel); no data-path collective; each rank
 renders K frames of its own (weak scaling); time = max over ranks.
 
-On the same JSON line (every BASELINE config that fits this box is timed by this one command):
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the line: the headline, its config, the
+per-rank step times and (train) the all-reduce figures its timed steps recorded.  Nothing else is run.
+
+With --full, on the same JSON line (every BASELINE config that fits this box is timed by this one command):
   roofline     -- the dominant kernel (fused MLP forward, fine pass: 65536 rays x 192 samples per launch), timed live with
                   HIP events on the launch stream; achieved = algorithmic FLOPs (1,100,032 per point) / average
                   launch duration, against the dense fp32-MFMA peak (157.3 TFLOP/s); `traffic` = HBM bytes per launch from
@@ -271,7 +275,7 @@ def bench_train(args, nerf, model_c, model_f, dev, rank, world, dist, emit=True)
         dump_outputs(args.dump_outputs, {"loss": loss, **dict(zip(RENDER_OUTPUTS, out)), "latent_codes": latent_codes,
                                          **{"coarse." + k: v for k, v in model_c.named_parameters()},
                                          **{"fine." + k: v for k, v in model_f.named_parameters()}})
-    roofline = train_roofline(args, model_f, dev, n_rays) if rank == 0 else None
+    roofline = train_roofline(args, model_f, dev, n_rays) if rank == 0 and args.full else None
     allreduce = reducer.stats()          # ranks the communicator saw, bytes per step, median HIP-event time of the collective
     result = None
     if rank == 0:
@@ -288,7 +292,7 @@ def bench_train(args, nerf, model_c, model_f, dev, rank, world, dist, emit=True)
                        "rays_per_step": n_rays * world, "parallelism": f"dp{world}",
                        "mlp_precision": args.precision, "family": args.family}}
         if emit:
-            result["config"]["device"] = device_info(dev)
+            result["config"]["device"] = device_info(dev, probes=args.full)
             result["summary"] = {"value_rays_s": result["value"], "ms_per_step": result["ms_per_step"], "n_gpus": world,
                                  "ranks_seen": allreduce["ranks_seen"], "allreduce_us": allreduce["allreduce_us"],
                                  "bytes_allreduced": allreduce["bytes_allreduced"], "mlp_precision": args.precision,
@@ -415,8 +419,11 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="headline + roofline only (skip split_bf16 / train / tiny / PMC traffic)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: the other arithmetics and their gate, training, tiny, rooflines, PMC "
+                         "passes, device probes, launcher leg, eager-ROCm and CPU baselines (a plain run times the headline only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the eager-ROCm and CPU baselines")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: headline + roofline only (skip split_bf16 / train / tiny / PMC traffic)")
     ap.add_argument("--precision", choices=["bf16x3", "f16x3", "f16x2", "f32"], default="f32",
                     help="arithmetic of the HEADLINE: f32 (default) = exact-f32 MFMA, the reference's arithmetic; f16x3 = split-fp16 "
                          "(3 fp16 MFMAs per product on scaled weights, f32 accumulate: error against fp64 at the exact-f32 kernel's "
@@ -552,12 +559,12 @@ def main():
         "config": {"workload": "configs[1]: paper-model eval forward, 512x512 frame, 64+128 samples, chunksize 65536, "
                                "perturb on, expression+latent conditioned, background prior; frames sharded over GPUs",
                    "rays_per_step": H * W, "points_per_ray": N_COARSE + N_COARSE + N_FINE, "parallelism": f"frames x{world}",
-                   "mlp_precision": args.precision, "device": device_info(dev)},
+                   "mlp_precision": args.precision, "device": device_info(dev, probes=args.full)},
     }
 
     # ---- the same K frames (same warm-up, same bracketing) in the other arithmetics, beside the headline -----------------
     others = [p for p in ("f32", "f16x3", "f16x2", "bf16x3") if p != args.precision]
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         for other in others:
             nerf.set_mlp_precision(other)
             dt_o, _, _ = timed_frames()
@@ -601,7 +608,7 @@ def main():
             torch.manual_seed(1234 + rank)
 
     # ---- configs[2] (N>1: configs[4]): training iterations in both arithmetics --------------------------------------------
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         train = {}
         keep_steps, keep_warm, keep_prec = args.steps, args.warmup, args.precision
         for prec in ("f32", "f16x3", "bf16x3"):
@@ -624,7 +631,7 @@ def main():
                 pmc_train_traffic(train)
                 train["clock_detail"] = pmc_train_clocks(train)
 
-    if rank == 0:
+    if rank == 0 and args.full:
         # ---- roofline of the dominant kernel: fused MLP forward, fine pass of one ray chunk ----------------
         S = N_COARSE + N_FINE
         pk = model_f.hip_weights().get()
@@ -751,6 +758,7 @@ def main():
                                                                       ("train_fwd_f32", lambda: ops.paper_mlp_fwd_train(pk, cond, ro[:2048], rd[:2048], z[:2048, :128].contiguous()))))
             except Exception as e:
                 line["config"]["device"]["power"] = {"error": repr(e)}
+    if rank == 0:
         line["ranks_seen"] = int(dist.get_world_size()) if dist is not None else 1
         line["per_rank_ms_per_step"] = per_rank_ms
         line["summary"] = summary_of(line)

@@ -68,10 +68,15 @@ def pattern_store_probe():
         return {"error": repr(e)}
 
 
-def device_info(dev):
+def device_info(dev, probes=True):
     """What the box reports (re-derive the peaks from the clocks of the GPU box): CUs x 256 fp32-MFMA FLOP per clock x
-    the engine clock, beside the vendor figure the roofline is priced against."""
+    the engine clock, beside the vendor figure the roofline is priced against.  probes=False (a plain bench run): only what torch
+    reports and the environment -- no rocminfo, no HBM probe."""
     p = torch.cuda.get_device_properties(dev)
+    env = {k: v for k, v in os.environ.items() if re.match(r"(HSA|HIP|ROCR|ROCM|GPU|AMD|PYTORCH|NCCL|RCCL)_", k)}   # what differs box to box
+    if not probes:
+        return {"env": env, "name": p.name, "arch": getattr(p, "gcnArchName", ""), "compute_units": int(p.multi_processor_count),
+                "hbm_gib": round(p.total_memory / 2 ** 30, 1)}
     mhz = float(getattr(p, "clock_rate", 0)) / 1e3
     if mhz <= 0:                                                        # torch on ROCm reports no clock: ask rocminfo (gfx agent's max clock)
         try:
@@ -102,7 +107,7 @@ def device_info(dev):
         torch.cuda.empty_cache()
     except Exception as e:
         probe = {"hbm_probe_error": repr(e)}
-    probe["env"] = {k: v for k, v in os.environ.items() if re.match(r"(HSA|HIP|ROCR|ROCM|GPU|AMD|PYTORCH|NCCL|RCCL)_", k)}   # what differs box to box
+    probe["env"] = env
     return {**probe, "name": p.name, "arch": getattr(p, "gcnArchName", ""), "compute_units": cus, "engine_clock_mhz": mhz,
             "hbm_gib": round(p.total_memory / 2 ** 30, 1),
             "fp32_mfma_peak_from_clock_tflops": cus * 256 * mhz * 1e6 / 1e12, "fp32_mfma_peak_priced_tflops": PEAK_F32_MFMA_TFLOPS}

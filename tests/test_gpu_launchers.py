@@ -159,7 +159,8 @@ def test_bench_two_ranks_one_gpu_gloo(hip_lib, gpu):
     env = dict(os.environ, NERFACE_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     port = 29700 + (os.getpid() % 1000)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--train-steps", "3"]
+           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--train-steps", "3",
+           "--full"]
     r = subprocess.run(cmd, env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
     from tests.util import parse_bench_stdout
@@ -234,6 +235,33 @@ def test_bench_dump_outputs(hip_lib, gpu, tmp_path):
     assert n_params == 2 * 568708 and float(np.abs(tr["latent_codes"]).sum()) > 0
 
 
+def test_bench_plain_run_times_the_headline_only(hip_lib, gpu):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` runs the headline's steps and nothing else: the line carries the contract's
+    keys, the per-rank step times and (train) the all-reduce figures of the timed steps; the other arithmetics, training, tiny,
+    rooflines, PMC passes, device probes and baselines are `--full` only."""
+    import subprocess
+    from tests.util import parse_bench_stdout
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "NERFACE_DIST_BACKEND", "NERFACE_DIST_FORCE"):
+        env.pop(k, None)
+    extras = ("roofline", "split_f16", "split_f16x2", "split_bf16", "exact_f32", "train", "tiny", "tiny4", "eager_rocm", "cpu_baseline",
+              "launcher", "whole_frame_parity_error")
+    for extra in ([], ["--mode", "train"]):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", *extra],
+                           env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+        assert r.returncode == 0, r.stderr.decode()[-3000:]
+        c, d = parse_bench_stdout(r.stdout.decode())
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert k in c and k in d, k
+        assert c["steps"] == d["steps"] == 2 and c["warmup"] == 1 and c["dtype"] == "f32" and c["value"] > 0 and c["ms_per_step"] > 0
+        assert not [k for k in extras if d.get(k) is not None], extras
+        assert not {"hbm_fill_gbs", "engine_clock_mhz", "power", "pattern_store"} & set(d["config"]["device"])
+        if extra:
+            assert d["ranks_seen"] == d["allreduce"]["ranks_seen"] == 1 and abs(d["value"] * d["ms_per_step"] * 1e-3 - 2048) < 1e-3
+        else:
+            assert abs(d["value"] * d["ms_per_step"] * 1e-3 - 512 * 512) < 1.0 and len(d["per_rank_ms_per_step"]) == 1
+
+
 def test_bench_more_ranks_than_devices_fails_fast_with_the_reason(hip_lib, gpu):
     """`bench.py --gpus N` with the nccl (RCCL) backend on a box with fewer than N devices must exit non-zero within a
     minute with a message naming device_count -- not hang in the rendezvous or inside ncclCommInitRank.  Both entry forms: the bare
@@ -285,7 +313,8 @@ def test_rccl_single_rank_runs_every_collective(hip_lib, gpu, tmp_path):
     rep = json.load(open(os.path.join(base, "logs", "synthetic", "dp_consistency.json")))
     assert rep["world"] == 1 and rep["iters"] == 3 and rep["identical_parameters"]
     assert "[DP] 1 ranks" in log and "[VAL] Iter: 0" in log
-    r = subprocess.run(_torchrun(1, port + 1) + [os.path.join(ROOT, "bench.py"), "--gpus", "1", "--mode", "train", "--steps", "3", "--warmup", "1"],
+    r = subprocess.run(_torchrun(1, port + 1) + [os.path.join(ROOT, "bench.py"), "--gpus", "1", "--mode", "train", "--steps", "3", "--warmup", "1",
+                                                 "--full"],
                        env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
     from tests.util import parse_bench_stdout
