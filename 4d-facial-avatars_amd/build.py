@@ -53,23 +53,11 @@ def _includes(src: str, seen=None) -> set:
     return seen
 
 
-def build_variant(suffix: str, extra_flags, verbose: bool = True) -> str:
-    """Experiment builds: lib/libnerface_hip_<suffix>.so compiled with extra -D switches (own object directory).  Selected at
-    run time with NERFACE_HIP_LIB=<path>; never loaded by default.  Used for same-session A/B kernel timings (profiles/)."""
-    global OUT
-    keep = OUT
-    OUT = os.path.join(OUT_DIR, f"libnerface_hip_{suffix}.so")
-    try:
-        return build(force=False, verbose=verbose, _extra=list(extra_flags), _obj=f"obj_{suffix}", _always=True)
-    finally:
-        OUT = keep
-
-
-def build(force: bool = False, verbose: bool = True, _extra=(), _obj="obj", _always=False) -> str:
-    if not force and not _always and not _stale():
+def build(force: bool = False, verbose: bool = True) -> str:
+    if not force and not _stale():
         return OUT
     os.makedirs(OUT_DIR, exist_ok=True)
-    obj_dir = os.path.join(OUT_DIR, _obj)                       # object cache (git-ignored): incremental rebuilds
+    obj_dir = os.path.join(OUT_DIR, "obj")                      # object cache (git-ignored): incremental rebuilds
     os.makedirs(obj_dir, exist_ok=True)
     objs = []
     cc = _hipcc()
@@ -85,7 +73,7 @@ def build(force: bool = False, verbose: bool = True, _extra=(), _obj="obj", _alw
             continue
         # -Rpass-analysis: per-kernel registers / spills / scratch / LDS as compiler remarks, kept beside the object
         # (lib/obj/<unit>.usage.txt; tests/test_host.py reads them: no kernel of the library may spill)
-        procs.append((s, subprocess.Popen([cc, *FLAGS, *UNIT_FLAGS.get(s, []), *_extra, "-Rpass-analysis=kernel-resource-usage", "-c", src, "-o", obj],
+        procs.append((s, subprocess.Popen([cc, *FLAGS, *UNIT_FLAGS.get(s, []), "-Rpass-analysis=kernel-resource-usage", "-c", src, "-o", obj],
                                           stdout=subprocess.PIPE, stderr=subprocess.STDOUT)))
     for s, p in procs:
         try:
@@ -131,8 +119,5 @@ def build_tools(verbose: bool = True):
 
 
 if __name__ == "__main__":
-    if len(sys.argv) > 2 and sys.argv[1] == "--variant":          # python build.py --variant NAME -DFOO=1 ...
-        print(build_variant(sys.argv[2], sys.argv[3:]))
-    else:
-        build(force="--force" in sys.argv)
-        build_tools()
+    build(force="--force" in sys.argv)
+    build_tools()

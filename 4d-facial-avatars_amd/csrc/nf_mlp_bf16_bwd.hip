@@ -14,9 +14,7 @@
 // point's largest gradient (block floating point, nf_mlp_bf16_machinery.inc) so that they sit at the top of fp16's exponent range.
 #if NFB_F16
 #define NFB_BWD_NAME(x) x##_f16
-#ifndef NFB_TILE_GROUP
 #define NFB_TILE_GROUP 4
-#endif
 #else
 #define NFB_BWD_NAME(x) x##_bf16
 #endif

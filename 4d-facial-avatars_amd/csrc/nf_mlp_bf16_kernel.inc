@@ -39,16 +39,9 @@ NFB_KERNEL_NAME(const char* __restrict__ wstream, const float* __restrict__ cond
 #define SC(L_) wsc[L_]
 #define INV(L_) wsc[nfb::NL + (L_)]
 #define OUT_INV(L_) (wsc[nfb::NL + (L_)] * (1.0f / ACT))
-#if NFB_EPI_OLD                                     // round-5 epilogue (A/B builds: python build.py --variant epi_old -DNFB_EPI_OLD=1)
-#define NFB_TO_OPERANDS(L_, acc_, NO_, RELU_) nfb_to_operands<NO_, RELU_, true>(acc_, bh, bl, 4, INV(L_))
-#define BSC(L_) SC(L_)
-#else
 #define NFB_TO_OPERANDS(L_, acc_, NO_, RELU_) nfb_to_operands_f16<NO_, RELU_>(acc_, bh, bl, 4, INV(L_), SC(L_) * (65504.0f / ACT))
-#define BSC(L_) 1.0f                                // the bias table in LDS is scaled once per workgroup (below)
-#endif
 #else
-#define NFB_TO_OPERANDS(L_, acc_, NO_, RELU_) nfb_to_operands<NO_, RELU_, false>(acc_, bh, bl, 4, 1.0f)
-#define BSC(L_) 1.0f
+#define NFB_TO_OPERANDS(L_, acc_, NO_, RELU_) nfb_to_operands<NO_, RELU_>(acc_, bh, bl, 4, 1.0f)
     constexpr float ACT = 1.0f;
 #define SC(L_) 1.0f
 #define INV(L_) 1.0f
@@ -127,7 +120,7 @@ NFB_KERNEL_NAME(const char* __restrict__ wstream, const float* __restrict__ cond
     nfb_wait_vm<nfb::inflight_after(-1)>();                            // bias + stage 0 landed (later stages may be in flight)
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
-#if NFB_F16 && !NFB_EPI_OLD
+#if NFB_F16
     {
         // the accumulators start from bias * (weight scale * activation scale): scaled HERE, once per workgroup and in LDS (ten
         // multiplies per thread), so that a layer's accumulator initialisation is four ds_read_b128 per tile and no vector
@@ -174,12 +167,12 @@ NFB_KERNEL_NAME(const char* __restrict__ wstream, const float* __restrict__ cond
 #define NFB_RUN(L_, acc_, oh_, ol_, NOP_, prev_, PSEC_) NFB_LAYER(L_, acc_, oh_, ol_)
 #endif
     // ---- layers_xyz.0 : PE -> 256 --------------------------------------------------------------------------
-    nfb_init_bias<8>(accA, bias + B_L0, h, BSC(0));
+    nfb_init_bias<8>(accA, bias + B_L0, h);
     NFB_LAYER(0, accA, bh, bl);
     NFB_FINISH(0, accA, 8, true, S_H0);
 #define NFB_HIDDEN_LAYER(L_, acc_, BIAS_, RELU_, SEC_, prev_, PSEC_)                 \
     do {                                                                             \
-        nfb_init_bias<8>(acc_, bias + (BIAS_), h, BSC(L_));                           \
+        nfb_init_bias<8>(acc_, bias + (BIAS_), h);                                   \
         _Pragma("unroll") for (int s = 0; s < 16; ++s) { th[s] = bh[4 + s]; tl[s] = bl[4 + s]; } \
         NFB_RUN(L_, acc_, th, tl, 8, prev_, PSEC_);                                  \
         NFB_FINISH(L_, acc_, 8, RELU_, SEC_);                                        \
@@ -187,7 +180,7 @@ NFB_KERNEL_NAME(const char* __restrict__ wstream, const float* __restrict__ cond
     NFB_HIDDEN_LAYER(1, accB, B_L1, true, S_H1, accA, S_H0);
     NFB_HIDDEN_LAYER(2, accA, B_L2, true, S_H2, accB, S_H1);
     // ---- layers_xyz.3 : [PE | h] (20 k-steps: operands 0..19 as they sit) ------------------------------------------
-    nfb_init_bias<8>(accB, bias + B_L3, h, BSC(3));
+    nfb_init_bias<8>(accB, bias + B_L3, h);
     NFB_RUN(3, accB, bh, bl, 8, accA, S_H2);
     NFB_FINISH(3, accB, 8, true, S_H3);
     NFB_HIDDEN_LAYER(4, accA, B_L4, true, S_H4, accB, S_H3);
@@ -195,9 +188,9 @@ NFB_KERNEL_NAME(const char* __restrict__ wstream, const float* __restrict__ cond
     NFB_HIDDEN_LAYER(6, accA, B_FEAT, false, S_FEAT, accB, S_H5);
 #undef NFB_HIDDEN_LAYER
     // ---- layers_dir.0 (+ fc_alpha as tile 4): 16 feat k-steps + dir k-step + 1 zero k-step ------------------------------
-    nfb_init_bias<4>(accB, bias + B_D0, h, BSC(7));
+    nfb_init_bias<4>(accB, bias + B_D0, h);
     nfb_zero(accB[4]);
-    if (h == 0) accB[4][0] = bias[B_D0 + 128] * BSC(7);
+    if (h == 0) accB[4][0] = bias[B_D0 + 128];
 #pragma unroll
     for (int s = 0; s < 16; ++s) { th[s] = bh[4 + s]; tl[s] = bl[4 + s]; }
     th[16] = dh; tl[16] = dl;
@@ -209,12 +202,12 @@ NFB_KERNEL_NAME(const char* __restrict__ wstream, const float* __restrict__ cond
     const float sigma_raw = accB[4][0] * OUT_INV(7);
     NFB_FINISH(7, accB, 4, true, S_D0);
     // ---- layers_dir.1, .2 ----------------------------------------------------------------------------------------------
-    nfb_init_bias<4>(accA, bias + B_D1, h, BSC(8));
+    nfb_init_bias<4>(accA, bias + B_D1, h);
 #pragma unroll
     for (int s = 0; s < 8; ++s) { th[s] = bh[4 + s]; tl[s] = bl[4 + s]; }
     NFB_RUN(8, accA, th, tl, 4, accB, S_D0);
     NFB_FINISH(8, accA, 4, true, S_D1);
-    nfb_init_bias<4>(accB, bias + B_D2, h, BSC(9));
+    nfb_init_bias<4>(accB, bias + B_D2, h);
 #pragma unroll
     for (int s = 0; s < 8; ++s) { th[s] = bh[4 + s]; tl[s] = bl[4 + s]; }
     NFB_RUN(9, accB, th, tl, 4, accA, S_D1);
@@ -243,6 +236,5 @@ NFB_KERNEL_NAME(const char* __restrict__ wstream, const float* __restrict__ cond
 #undef INV
 #undef OUT_INV
 #undef NFB_TO_OPERANDS
-#undef BSC
 }
 

@@ -9,16 +9,10 @@
 // end-of-stage wait is a COUNTED s_waitcnt vmcnt(n) that leaves exactly that newest group in flight across the
 // (raw) workgroup barrier.  Per-call biases are DMA'd once into LDS so that no ordinary global load (whose
 // compiler-inserted vmcnt(0) would drain the pipeline) remains in the layer loop.  All LDS lives in ONE array.
-#ifndef NFB_KPS
 #define NFB_KPS 2                                   // k-steps per stage
-#endif
 #define NFB_STAGE_BYTES (NFB_KPS * 8 * 2 * 1024)    // largest stage: 8 tiles x (hi, lo) x 1 KiB per k-step = 32 KiB
-#ifndef NFB_NBUF
 #define NFB_NBUF 4                                  // ring depth; stage g + NFB_NBUF - 1 is prefetched while stage g is consumed
-#endif
-#ifndef NFB_STAGGER_DIV
 #define NFB_STAGGER_DIV 4                           // wave w issues its DMA burst after w / DIV of the stage's MFMAs
-#endif
 #define NFB_LA (NFB_NBUF - 1)
 #define NFB_BIAS_BLOCKS 10                          // cond table (2332 f32) padded to 10 KiB
 #define NFB_XPOSE_PITCH 144                          // bytes per staged point row (128 + 16: conflict-free ds_write_b128)
@@ -114,9 +108,7 @@ __device__ __forceinline__ NfbSaveTarget nfb_save_target(float* sec, int width, 
     return t;
 }
 typedef unsigned nfb_u32x4 __attribute__((ext_vector_type(4)));
-#ifndef NFB_SAVE_AUX
 #define NFB_SAVE_AUX 2                                      // nt: the saves are read next by another kernel, from HBM
-#endif
 __device__ __forceinline__ void nfb_tile_to_slab(char* slab, const f32x16& a, int lane) {
     const int h = lane >> 5, c = lane & 31;
     *reinterpret_cast<f32x4*>(slab + c * NFB_XPOSE_PITCH + (0 + 4 * h) * 4) = (f32x4){a[0], a[1], a[2], a[3]};
@@ -319,10 +311,7 @@ __device__ __forceinline__ void nfb_stage(const NfbCtx& cx, f32x16 (&acc)[8], co
 #pragma unroll
                 for (int nt = 0; nt < TG; ++nt) {
                     if (!((PM >> t) & 1)) continue;
-#ifndef NFB_NO_DMA
-#define NFB_NO_DMA 0                                          // 1: timing ablation -- no weight DMA inside the layers (stale ring, WRONG results)
-#endif
-                    if (nb2 > 0 && !NFB_NO_DMA) {
+                    if (nb2 > 0) {
 #pragma unroll
                         for (int w = 0; w < 4; ++w)
                             if (m == (w * NM) / NFB_STAGGER_DIV && cx.wave == w)
@@ -370,10 +359,8 @@ __device__ __forceinline__ void nfb_split(const float (&x)[8], bf16x8& hi, bf16x
 }
 
 // accumulators (NO tiles) -> B operands of the next layer: tile nt, regs 8u..8u+7 -> k-step 2 nt + u
-// `inv` un-does the layer's weight scale (fp16 instantiation; exactly 1 and folded away for bf16).  SAT (fp16): the ReLU's
-// med3 clamps at fp16's largest finite value instead of +inf -- same instruction, and an out-of-range activation saturates
-// instead of turning into inf -> NaN -> (next layer's ReLU) 0.
-template <int NO, bool RELU, bool SAT = false>
+// `inv` un-does the layer's weight scale (fp16 instantiation; exactly 1 and folded away for bf16).
+template <int NO, bool RELU>
 __device__ __forceinline__ void nfb_to_operands(const f32x16 (&acc)[8], bf16x8 (&bh)[20], bf16x8 (&bl)[20], int s_off, float inv = 1.0f) {
 #pragma unroll
     for (int nt = 0; nt < NO; ++nt)
@@ -383,7 +370,7 @@ __device__ __forceinline__ void nfb_to_operands(const f32x16 (&acc)[8], bf16x8 (
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 const float v = acc[nt][8 * u + j] * inv;
-                x[j] = RELU ? __builtin_amdgcn_fmed3f(v, 0.f, SAT ? 65504.0f : __builtin_inff()) : v;
+                x[j] = RELU ? __builtin_amdgcn_fmed3f(v, 0.f, __builtin_inff()) : v;
             }
             nfb_split(x, bh[s_off + 2 * nt + u], bl[s_off + 2 * nt + u]);
         }
@@ -503,13 +490,13 @@ __device__ __forceinline__ void nfb_scale(f32x16 (&acc)[8], float s) {
 
 // acc[nt] reg r <- bias[32 nt + (r&3) + 8 (r>>2) + 4 h]   (bias table in LDS)
 template <int NO>
-__device__ __forceinline__ void nfb_init_bias(f32x16 (&acc)[8], const float* bias, int h, float sc = 1.0f) {
+__device__ __forceinline__ void nfb_init_bias(f32x16 (&acc)[8], const float* bias, int h) {
 #pragma unroll
     for (int nt = 0; nt < NO; ++nt)
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const f32x4 b = *reinterpret_cast<const f32x4*>(bias + 32 * nt + 8 * q + 4 * h);
-            acc[nt][4 * q + 0] = b.x * sc; acc[nt][4 * q + 1] = b.y * sc; acc[nt][4 * q + 2] = b.z * sc; acc[nt][4 * q + 3] = b.w * sc;
+            acc[nt][4 * q + 0] = b.x; acc[nt][4 * q + 1] = b.y; acc[nt][4 * q + 2] = b.z; acc[nt][4 * q + 3] = b.w;
         }
 }
 

@@ -121,7 +121,7 @@ k_dw_gemm(const NfDwJob* __restrict__ jobs, int n_jobs, int slab_floats, const f
 // a GROUP of four 128 x 128 products that read common operand panels (the 2 x 2 blocks of one 256 x 256 product; the four
 // products against the positional encoding; ...):
 //   * a panel = 16 points x 128 columns of dZ / d_raw / saved activations = 8 KiB; the group's panels of a 16-point chunk are
-//     fetched ONCE per workgroup, by LDS-DMA (global_load_lds_dwordx4: two full rows = 1 KiB per wave instruction, no registers
+//     fetched ONCE per workgroup, by LDS-DMA (buffer_load_dwordx4 ... lds: two full rows = 1 KiB per wave instruction, no registers
 //     in between), into a three-stage ring, three chunks ahead of the MFMAs.  k_dw_gemm fetched every panel once per JOB (twice
 //     per 256 x 256 layer: 35 KB per point against 17.7 KB of distinct data, 3.2 TB/s) through 64 staging registers;
 //   * eight waves, two per SIMD: wave 2 j + h owns the 128 x 64 half h of product j (128 accumulator registers, 48 operand
@@ -252,17 +252,12 @@ k_dw_gemm_lds(NfDwGroupSet gs, int slab_floats, const float* __restrict__ dz, co
     const int n_full = n_rows >> 4;                   // whole 16-point chunks (block-uniform): the pipelined loop
     float* out = slabs + (int64_t)slice * slab_floats + job.out_off;
 
-    // ---- DMA: piece (panel s, j) moves rows 2 j, 2 j + 1 of the chunk; wave w issues piece j = w of every panel.
-    // Every lane keeps its 6 source pointers and advances them by one chunk per issue.  Lanes past a narrow panel's `valid`
-    // columns re-read its last valid piece: those columns only feed output tiles nobody stores.
-    const int dma_row = lane >> 5, dma_col = (lane & 31) * 4;
-#ifndef NF_DW_BUFFER_DMA
-#define NF_DW_BUFFER_DMA 1
-#endif
-#if NF_DW_BUFFER_DMA
-    // Buffer form of the DMA: per panel one descriptor based at the slice's first row, the lane's part of the address in ONE VGPR
-    // that never changes, and the chunk offset in an SGPR advanced by scalar adds -- no 64-bit vector address per panel, no
+    // ---- DMA: piece (panel s, j) moves rows 2 j, 2 j + 1 of the chunk; wave w issues piece j = w of every panel.  Lanes past a
+    // narrow panel's `valid` columns re-read its last valid piece: those columns only feed output tiles nobody stores.
+    // Per panel one buffer descriptor based at the slice's first row, the lane's part of the address in ONE VGPR that never
+    // changes, and the chunk offset in an SGPR advanced by one chunk per issue -- no 64-bit vector address per panel, no
     // v_add_co / v_addc per issue.
+    const int dma_row = lane >> 5, dma_col = (lane & 31) * 4;
     __amdgpu_buffer_rsrc_t rs[NF_DW_MAXP];
     int voff[NF_DW_MAXP], soff[NF_DW_MAXP], step_b[NF_DW_MAXP];
 #pragma unroll
@@ -278,34 +273,13 @@ k_dw_gemm_lds(NfDwGroupSet gs, int slab_floats, const float* __restrict__ dz, co
         rs[s] = __builtin_amdgcn_make_buffer_rsrc(on ? const_cast<float*>(base + p_begin * ld) : const_cast<float*>(nf_dw_zero16), (short)0, on ? -1 : 16,
                                                   0x00020000);
     }
+    // issue this wave's piece of panel s of the next chunk into `stage`; with advance = false the offset stays (dummy issues
+    // past the last chunk re-read it: harmless, and the counted waits stay uniform)
     auto issue_piece = [&](int s, int stage, bool advance) {
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rs[s], (__attribute__((address_space(3))) void*)(lds + stage * NF_DW_STAGE_BYTES + wave * 1024 + s * NF_DW_PANEL_BYTES),
                                                  16, voff[s], soff[s], 0, 0);
         soff[s] += advance ? step_b[s] : 0;
     };
-#else
-    const char* src[NF_DW_MAXP];               // source of the NEXT chunk to issue
-    int step_b[NF_DW_MAXP];                    // bytes per chunk (wave-uniform)
-#pragma unroll
-    for (int s = 0; s < NF_DW_MAXP; ++s) {
-        const NfDwPanel pn = grp.panel[s];
-        const bool on = pn.kind >= 0;
-        const float* base = pn.kind == 1 ? d_raw : ((pn.kind == 0 ? dz : saved) + (int64_t)pn.sec * n_points);
-        const int ld = on ? pn.ld : 0;
-        const int col = on ? (dma_col < pn.valid ? dma_col : pn.valid - 4) : 0;
-        step_b[s] = 64 * ld;
-        src[s] = on ? reinterpret_cast<const char*>(base + (p_begin + 2 * wave + dma_row) * ld + pn.col0 + col)
-                    : reinterpret_cast<const char*>(nf_dw_zero16);
-    }
-    // issue this wave's piece of panel s of the next chunk into `stage`; with advance = false the pointer stays (dummy issues
-    // past the last chunk re-read it: harmless, and the counted waits stay uniform)
-    auto issue_piece = [&](int s, int stage, bool advance) {
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src[s],
-                                         (__attribute__((address_space(3))) void*)(lds + stage * NF_DW_STAGE_BYTES + wave * 1024 + s * NF_DW_PANEL_BYTES),
-                                         16, 0, 0);
-        src[s] += advance ? step_b[s] : 0;
-    };
-#endif
     auto issue = [&](int stage, bool advance) {
 #pragma unroll
         for (int s = 0; s < NF_DW_MAXP; ++s) issue_piece(s, stage, advance);
@@ -367,14 +341,9 @@ k_dw_gemm_lds(NfDwGroupSet gs, int slab_floats, const float* __restrict__ dz, co
                 // 3 operand registers from chunk c + 1 -- issued right behind the MFMAs that read them.  The LAST step's refill
                 // would sit right in front of the barrier (its LDS round trip in the path of all eight waves): it is read early, into
                 // three staging registers behind step 0, and moved over after step 3's MFMAs.
-#ifndef NF_DW_NO_STAGGER
                 // The two waves of a SIMD (the halves of one product) run this stream side by side, and a DMA piece holds its wave's
                 // issue for ~100 cycles: half 1 starts every chunk 8 MFMA slots late (its partner has the pipe to itself meanwhile).
-#ifndef NF_DW_STAGGER_SLEEP
-#define NF_DW_STAGGER_SLEEP 4                                        // x 64 cycles
-#endif
-                if (half) __builtin_amdgcn_s_sleep(NF_DW_STAGGER_SLEEP);
-#endif
+                if (half) __builtin_amdgcn_s_sleep(4);                       // 4 x 64 cycles
                 if (want_cs) {   // column sums of this chunk's A operands (bias gradients), before the refills overwrite them
 #pragma unroll
                     for (int r = 0; r < 4; ++r) { cs[0] += a0[r][0]; cs[1] += a0[r][1]; }

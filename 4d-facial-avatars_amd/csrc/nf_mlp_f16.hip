@@ -14,12 +14,8 @@
 #include <mutex>
 
 #define NFB_F16 1
-#ifndef NFB_TILE_GROUP
 #define NFB_TILE_GROUP 4          // A fragments of 4 output tiles at a time: 508 VGPRs, no spills (8 at a time: 42 spilled registers)
-#endif
-#ifndef NFB_ACT_SHIFT
 #define NFB_ACT_SHIFT 4
-#endif
 #include "nf_mlp_bf16_common.h"
 #include "nf_pack.h"
 

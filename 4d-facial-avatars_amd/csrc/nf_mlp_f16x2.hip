@@ -16,12 +16,8 @@
 
 #define NFB_F16 1
 #define NFB_PRODUCTS 5            // bit 0: W_lo x_hi, bit 2: W_hi x_hi
-#ifndef NFB_TILE_GROUP
 #define NFB_TILE_GROUP 4
-#endif
-#ifndef NFB_ACT_SHIFT
 #define NFB_ACT_SHIFT 4
-#endif
 #include "nf_mlp_bf16_common.h"
 #include "nf_pack.h"
 

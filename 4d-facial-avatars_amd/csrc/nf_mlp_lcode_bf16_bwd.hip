@@ -12,9 +12,7 @@
 // NFB_F16 = 1 (nf_mlp_lcode_f16_bwd.hip includes this file): the same chain on fp16 operand pairs, see nf_mlp_bf16_bwd.hip
 #if NFB_F16
 #define NFB_BWD_NAME(x) x##_f16
-#ifndef NFB_TILE_GROUP
 #define NFB_TILE_GROUP 4
-#endif
 #else
 #define NFB_BWD_NAME(x) x##_bf16
 #endif

@@ -34,16 +34,9 @@ NFB_KERNEL_NAME(const char* __restrict__ wstream, const float* __restrict__ cond
 #define SC(L_) wsc[L_]
 #define INV(L_) wsc[nfb::NL + (L_)]
 #define OUT_INV(L_) (wsc[nfb::NL + (L_)] * (1.0f / ACT))
-#if NFB_EPI_OLD                                     // round-5 epilogue (A/B builds, see nf_mlp_bf16_kernel.inc)
-#define NFB_TO_OPERANDS(L_, acc_, NO_, RELU_) nfb_to_operands<NO_, RELU_, true>(acc_, bh, bl, 4, INV(L_))
-#define BSC(L_) SC(L_)
-#else
 #define NFB_TO_OPERANDS(L_, acc_, NO_, RELU_) nfb_to_operands_f16<NO_, RELU_>(acc_, bh, bl, 4, INV(L_), SC(L_) * (65504.0f / ACT))
-#define BSC(L_) 1.0f                                // the bias table in LDS is scaled once per workgroup (below)
-#endif
 #else
-#define NFB_TO_OPERANDS(L_, acc_, NO_, RELU_) nfb_to_operands<NO_, RELU_, false>(acc_, bh, bl, 4, 1.0f)
-#define BSC(L_) 1.0f
+#define NFB_TO_OPERANDS(L_, acc_, NO_, RELU_) nfb_to_operands<NO_, RELU_>(acc_, bh, bl, 4, 1.0f)
     constexpr float ACT = 1.0f;
 #define SC(L_) 1.0f
 #define INV(L_) 1.0f
@@ -121,7 +114,7 @@ NFB_KERNEL_NAME(const char* __restrict__ wstream, const float* __restrict__ cond
     nfb_wait_vm<nfb::inflight_after(-1)>();                            // bias + stage 0 landed (later stages may be in flight)
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
-#if NFB_F16 && !NFB_EPI_OLD
+#if NFB_F16
     {
         // bias table scaled once per workgroup, in LDS (see nf_mlp_bf16_kernel.inc): layer l of the stream <-> its bias section
         float* bw = const_cast<float*>(bias);
@@ -168,12 +161,12 @@ NFB_KERNEL_NAME(const char* __restrict__ wstream, const float* __restrict__ cond
 #define NFB_LC_RUN(L_, acc_, oh_, ol_, NOP_, prev_, PSEC_) NFB_LAYER(L_, acc_, oh_, ol_)
 #endif
     // ---- layer1: PE -> 256, no activation (M:609) -----------------------------------------------------------------------
-    nfb_init_bias<8>(accA, bias + B_L1, h, BSC(0));
+    nfb_init_bias<8>(accA, bias + B_L1, h);
     NFB_LAYER(0, accA, bh, bl);
     NFB_LC_FINISH(0, accA, 8, false, 0);
 #define NFB_LC_HIDDEN(L_, acc_, BIAS_, MASK_, prev_, PSEC_)                          \
     do {                                                                             \
-        nfb_init_bias<8>(acc_, bias + (BIAS_), h, BSC(L_));                           \
+        nfb_init_bias<8>(acc_, bias + (BIAS_), h);                                   \
         _Pragma("unroll") for (int s = 0; s < 16; ++s) { th[s] = bh[4 + s]; tl[s] = bl[4 + s]; } \
         NFB_LC_RUN(L_, acc_, th, tl, 8, prev_, PSEC_);                               \
         NFB_LC_FINISH(L_, acc_, 8, true, MASK_);                                     \
@@ -186,15 +179,15 @@ NFB_KERNEL_NAME(const char* __restrict__ wstream, const float* __restrict__ cond
 #pragma unroll
     for (int s = 0; s < 16; ++s) { th[s] = bh[4 + s]; tl[s] = bl[4 + s]; }
     nfb_zero(accA[0]);
-    if (h == 0) accA[0][0] = bias[B_ALPHA] * BSC(4);
+    if (h == 0) accA[0][0] = bias[B_ALPHA];
     NFB_LAYER(4, accA, th, tl);
     const float sigma_raw = accA[0][0] * OUT_INV(4);
-    nfb_init_bias<8>(accA, bias + B_FEAT, h, BSC(5));
+    nfb_init_bias<8>(accA, bias + B_FEAT, h);
     NFB_LC_RUN(5, accA, th, tl, 8, accB, S_X2);
     NFB_LC_FINISH(5, accA, 8, true, 3);
 #undef NFB_LC_HIDDEN
     // ---- layers_dir.0: 16 feat k-steps + dir k-step + 1 zero k-step -> 128, ReLU -----------------------------------------
-    nfb_init_bias<4>(accB, bias + B_DIR, h, BSC(6));
+    nfb_init_bias<4>(accB, bias + B_DIR, h);
 #pragma unroll
     for (int s = 0; s < 16; ++s) { th[s] = bh[4 + s]; tl[s] = bl[4 + s]; }
     th[16] = dh; tl[16] = dl;
@@ -224,6 +217,5 @@ NFB_KERNEL_NAME(const char* __restrict__ wstream, const float* __restrict__ cond
 #undef INV
 #undef OUT_INV
 #undef NFB_TO_OPERANDS
-#undef BSC
 }
 

@@ -5,12 +5,8 @@
 #include <mutex>
 
 #define NFB_F16 1
-#ifndef NFB_TILE_GROUP
 #define NFB_TILE_GROUP 4
-#endif
-#ifndef NFB_ACT_SHIFT
 #define NFB_ACT_SHIFT 4
-#endif
 #include "nf_mlp_lcode_bf16_common.h"
 #include "nf_pack.h"
 
