@@ -1,7 +1,8 @@
 """Tensor-level wrappers over the C ABI (one function per entry point of include/nerface_hip.h).
 
 These allocate outputs with torch, pass raw device pointers + the current HIP stream, and translate
-non-zero return codes into RuntimeError.  No numerical work happens in Python.
+non-zero return codes into RuntimeError; sizes beyond a render kernel's compile-time limit are refused by name (ValueError) before
+anything is allocated.  No numerical work happens in Python.
 """
 from __future__ import annotations
 
@@ -546,6 +547,41 @@ def check_f16_range(*models, sync_ranks: bool = False) -> None:
                            'not finite -- render this model with "f32" or "bf16x3"')
 
 
+# ---------------------------------------------------------------------------------------- size limits of the render kernels
+# csrc/nf_render.hip sizes its wave-private LDS tables and its per-chunk register arrays at compile time (tests/test_host.py holds
+# these three numbers to the #defines there).  The C entry points answer a larger size with NF_EINVAL; the wrappers below refuse it
+# first, by name, before anything is allocated or launched.
+MAX_BINS = 512                       # NF_MAX_BINS: entries of the inverse-CDF table (K6, and the coarse mid-points of resample_merge)
+MAX_SORT = 1024                      # NF_MAX_SORT: columns of one sorted row (K7, and coarse + fine depths of resample_merge)
+MAX_BWD_SAMPLES = 1024               # 64 * NF_MAX_CHUNKS: samples per ray of the integrator's BACKWARD (the forward has no limit)
+
+
+def _refuse(what: str, got: str, limit: str) -> None:
+    raise ValueError(f"{what}: {got} exceeds {limit} (csrc/nf_render.hip); there is no kernel for this size")
+
+
+def check_resample_sizes(n_coarse: int, n_fine: int, what: str = "resample_merge") -> None:
+    if n_coarse - 1 > MAX_BINS:
+        _refuse(what, f"{n_coarse} coarse samples ({n_coarse - 1} bins)", f"the sampler's table limit NF_MAX_BINS = {MAX_BINS}")
+    if n_coarse + n_fine > MAX_SORT:
+        _refuse(what, f"{n_coarse} + {n_fine} = {n_coarse + n_fine} samples per ray", f"the row-sort limit NF_MAX_SORT = {MAX_SORT}")
+
+
+def check_bwd_samples(n_samples: int, what: str = "volume_render_bwd") -> None:
+    if n_samples > MAX_BWD_SAMPLES:
+        _refuse(what, f"{n_samples} samples per ray",
+                f"the integrator backward's limit of NF_MAX_CHUNKS = {MAX_BWD_SAMPLES // 64} chunks of 64 = {MAX_BWD_SAMPLES}")
+
+
+def check_sample_counts(n_coarse: int, n_fine: int, need_grad: bool) -> None:
+    """What run_one_iter_of_nerf checks before its first launch: a fine pass needs the resample + merge kernel's sizes, a training
+    step the integrator backward's (the forward integrator loops over chunks at run time and takes any count)."""
+    if n_fine > 0:
+        check_resample_sizes(n_coarse, n_fine, "run_one_iter_of_nerf (num_coarse + num_fine)")
+    if need_grad:
+        check_bwd_samples(n_coarse + max(n_fine, 0), "run_one_iter_of_nerf (training step)")
+
+
 # ---------------------------------------------------------------------------------------- K5
 def volume_render_fwd(raw, z, rd, noise=None, bg=None, white_background=False):
     dev = H.require_device(raw, z, rd, noise, bg)
@@ -565,11 +601,39 @@ def volume_render_bwd(raw, z, rd, noise, bg, d_rgb, white_background=False):
     d_rgb = _c(d_rgb)
     dev = H.require_device(raw, z, rd, noise, bg, d_rgb)
     n_rays, n_samples = z.shape
+    check_bwd_samples(n_samples)
     d_raw = torch.empty((n_rays, n_samples, 4), dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
         H.check(H.lib().nf_volume_render_bwd(H.ptr(raw), H.ptr(z), H.ptr(rd), H.ptr(noise), H.ptr(bg), H.ptr(d_rgb), n_rays,
                                              n_samples, 1 if white_background else 0, H.ptr(d_raw), H.stream_ptr(dev)),
                 "nf_volume_render_bwd")
+    return d_raw
+
+
+def render_volume_density(raw, depth):
+    """tiny_nerf's compositing (TN:68-107: no background sample, no +1e-6, spacing not scaled by |rd|): raw (n_rays, S, 4),
+    depth (n_rays, S) -> (rgb_map (n_rays, 3), depth_map (n_rays), acc_map (n_rays))."""
+    dev = H.require_device(raw, depth)
+    n_rays, n_samples = depth.shape
+    rgb = torch.empty((n_rays, 3), dtype=torch.float32, device=dev)
+    dmap = torch.empty((n_rays,), dtype=torch.float32, device=dev)
+    acc = torch.empty((n_rays,), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        H.check(H.lib().nf_render_volume_density(H.ptr(raw), H.ptr(depth), n_rays, n_samples, H.ptr(rgb), H.ptr(dmap), H.ptr(acc),
+                                                 H.stream_ptr(dev)), "nf_render_volume_density")
+    return rgb, dmap, acc
+
+
+def render_volume_density_bwd(raw, depth, d_rgb):
+    """Backward of render_volume_density for its rgb output: d_rgb (n_rays, 3) -> d_raw (n_rays, S, 4)."""
+    d_rgb = _c(d_rgb)
+    dev = H.require_device(raw, depth, d_rgb)
+    n_rays, n_samples = depth.shape
+    check_bwd_samples(n_samples, "render_volume_density_bwd")
+    d_raw = torch.empty((n_rays, n_samples, 4), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        H.check(H.lib().nf_render_volume_density_bwd(H.ptr(raw), H.ptr(depth), H.ptr(d_rgb), n_rays, n_samples, H.ptr(d_raw),
+                                                     H.stream_ptr(dev)), "nf_render_volume_density_bwd")
     return d_raw
 
 
@@ -639,6 +703,8 @@ def sample_pdf(bins, weights, n_out: int, u: Optional[torch.Tensor] = None, want
     dev = H.require_device(bins, weights)
     n_rays, n_bins = bins.shape
     assert weights.shape == (n_rays, n_bins - 1)
+    if n_bins > MAX_BINS:
+        _refuse("sample_pdf", f"{n_bins} bins", f"the sampler's table limit NF_MAX_BINS = {MAX_BINS}")
     u_t, stride = _u_arg(u, n_rays, n_out, dev)
     out = torch.empty((n_rays, n_out), dtype=torch.float32, device=dev)
     inds = torch.empty((n_rays, n_out), dtype=torch.int32, device=dev) if want_table else None
@@ -652,6 +718,7 @@ def sample_pdf(bins, weights, n_out: int, u: Optional[torch.Tensor] = None, want
 def resample_merge(z_coarse, w_coarse, n_fine: int, u: Optional[torch.Tensor] = None, want_samples: bool = False):
     dev = H.require_device(z_coarse, w_coarse)
     n_rays, n_coarse = z_coarse.shape
+    check_resample_sizes(n_coarse, n_fine)
     u_t, stride = _u_arg(u, n_rays, n_fine, dev)
     z_fine = torch.empty((n_rays, n_coarse + n_fine), dtype=torch.float32, device=dev)
     z_s = torch.empty((n_rays, n_fine), dtype=torch.float32, device=dev) if want_samples else None
@@ -665,6 +732,8 @@ def sort_rows(x: torch.Tensor) -> torch.Tensor:
     x = _c(x)
     dev = H.require_device(x)
     n_cols = x.shape[-1]
+    if n_cols > MAX_SORT:
+        _refuse("sort_rows", f"{n_cols} columns", f"the row-sort limit NF_MAX_SORT = {MAX_SORT}")
     rows = x.numel() // n_cols
     out = torch.empty_like(x)
     with torch.cuda.device(dev):

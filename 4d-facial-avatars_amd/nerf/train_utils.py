@@ -166,6 +166,12 @@ def _render_rays(ro, rd, rd_view, model_coarse, model_fine, options, mode, expre
     near, far = float(options.dataset.near), float(options.dataset.far)
     has_fine = nf > 0 and model_fine is not None
     noise_std = float(m.radiance_field_noise_std)
+    params_c = model_coarse.hip_param_list()
+    params_f = model_fine.hip_param_list() if has_fine else []
+    need_grad = torch.is_grad_enabled() and (latent_code.requires_grad or any(p.requires_grad for p in params_c + params_f))
+    # sample counts no render kernel is built for are refused here: before a random number is drawn or a kernel launched (the forward
+    # integrator takes any count, so without this a training step beyond the backward's limit would only fail inside backward())
+    ops.check_sample_counts(nc, nf if has_fine else 0, need_grad)
     # ---- random draws, in the reference's order and shapes (T:75, V:41-50, H:363-367) --------------
     t_rand = torch.rand((n_rays, nc), dtype=torch.float32, device=dev) if m.perturb else None
     noise_c = (torch.randn((n_rays, nc), dtype=torch.float32, device=dev) * noise_std) if noise_std > 0.0 else None
@@ -178,10 +184,7 @@ def _render_rays(ro, rd, rd_view, model_coarse, model_fine, options, mode, expre
     bg = None
     if background_prior is not None:
         bg = background_prior.to(device=dev, dtype=torch.float32).reshape(-1, 3).contiguous()
-    params_c = model_coarse.hip_param_list()
-    params_f = model_fine.hip_param_list() if has_fine else []
     expr = expressions.to(device=dev, dtype=torch.float32).reshape(-1).contiguous()
-    need_grad = torch.is_grad_enabled() and (latent_code.requires_grad or any(p.requires_grad for p in params_c + params_f))
     cfg = dict(model_coarse=model_coarse, model_fine=model_fine if has_fine else None, near=near, far=far, num_coarse=nc,
                lindisp=bool(m.lindisp),
                num_fine=nf if has_fine else 0, white_background=bool(m.white_background), need_grad=need_grad)

@@ -21,6 +21,7 @@ import torch
 
 from nerf import _hip as H
 from nerf import get_minibatches, get_ray_bundle, positional_encoding  # noqa: F401  (same imports as the reference script)
+from nerf import ops
 from nerf.models import FlexibleNeRFModel
 from nerf.ops import _c, bump_pack_epoch, pack_epoch
 
@@ -47,14 +48,7 @@ def render_volume_density(radiance_field, ray_origins, depth_values):
     S = raw.shape[-2]
     lead = raw.shape[:-2]
     depth = _c(depth_values.expand(*lead, S)) if depth_values.dim() > 1 else _c(depth_values.expand(*lead, S))
-    dev = H.require_device(raw, depth)
-    n = raw.numel() // (4 * S)
-    rgb = torch.empty((n, 3), dtype=torch.float32, device=dev)
-    dmap = torch.empty((n,), dtype=torch.float32, device=dev)
-    acc = torch.empty((n,), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        H.check(H.lib().nf_render_volume_density(H.ptr(raw), H.ptr(depth), n, S, H.ptr(rgb), H.ptr(dmap), H.ptr(acc),
-                                                 H.stream_ptr(dev)), "nf_render_volume_density")
+    rgb, dmap, acc = ops.render_volume_density(raw.reshape(-1, S, 4), depth.reshape(-1, S))
     return rgb.reshape(*lead, 3), dmap.reshape(lead), acc.reshape(lead)
 
 
@@ -130,6 +124,7 @@ class _TinyRender(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, model, ro, rd, depth, n_samples, *params):
+        ops.check_bwd_samples(n_samples, "run_one_iter_of_tinynerf (training step)")     # before the forward: backward() would refuse it
         dev = ro.device
         n = ro.shape[0]
         lib = H.lib()

@@ -405,6 +405,20 @@ def flex_mlp(p, x):
     return _lin(h, p, "fc_out")
 
 
+def render_volume_density(raw: torch.Tensor, depth: torch.Tensor):
+    """tiny_nerf's compositing (TN:68-107): raw (..., S, 4), depth (..., S) -> (rgb_map, depth_map, acc_map).  Unlike volume_render:
+    every colour goes through the sigmoid, no +1e-6 on the last density, the spacing is not scaled by |rd|."""
+    sigma = torch.relu(raw[..., 3])
+    rgb = torch.sigmoid(raw[..., :3])
+    big = torch.full_like(depth[..., :1], 1e10)
+    dists = torch.cat((depth[..., 1:] - depth[..., :-1], big), dim=-1)
+    alpha = 1.0 - torch.exp(-sigma * dists)
+    trans = torch.cumprod(1.0 - alpha + 1e-10, dim=-1)
+    trans = torch.cat((torch.ones_like(trans[..., :1]), trans[..., :-1]), dim=-1)
+    w = alpha * trans
+    return (w[..., None] * rgb).sum(dim=-2), (w * depth).sum(dim=-1), w.sum(dim=-1)
+
+
 def tiny_render(p, height, width, focal, c2w, near, far, n_samples, n_freq=10, jitter: Optional[torch.Tensor] = None):
     """run_one_iter_of_tinynerf (TN:111-159): whole image, coarse only, no background prior,
     no +1e-6, no |rd| scaling (TN:68-107).  `p`: VeryTinyNerfModel's state_dict (TN:162-181) or, with a "fc_out.weight" entry,
@@ -423,15 +437,7 @@ def tiny_render(p, height, width, focal, c2w, near, far, n_samples, n_freq=10, j
         h = torch.relu(_lin(x, p, "layer1"))
         h = torch.relu(_lin(h, p, "layer2"))
         raw = _lin(h, p, "layer3").reshape(height, width, n_samples, 4)
-    sigma = torch.relu(raw[..., 3])
-    rgb = torch.sigmoid(raw[..., :3])
-    big = torch.full_like(depth[..., :1], 1e10)
-    dists = torch.cat((depth[..., 1:] - depth[..., :-1], big), dim=-1)
-    alpha = 1.0 - torch.exp(-sigma * dists)
-    trans = torch.cumprod(1.0 - alpha + 1e-10, dim=-1)
-    trans = torch.cat((torch.ones_like(trans[..., :1]), trans[..., :-1]), dim=-1)
-    w = alpha * trans
-    return (w[..., None] * rgb).sum(dim=-2), (w * depth).sum(dim=-1), w.sum(dim=-1)
+    return render_volume_density(raw, depth)
 
 
 # --------------------------------------------------------------------------------------

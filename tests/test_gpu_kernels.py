@@ -555,6 +555,40 @@ def test_one_launch_adam_follows_torch_adam(hip_lib, gpu):
             assert float((c_ - b).abs().max() / (b.abs().max() + 1e-12)) < 2e-6, k
 
 
+def test_one_launch_adam_beyond_64_tensors(hip_lib, gpu):
+    """nf_adam_step hands the kernel at most 64 tensors (NF_ADAM_MAX_TENSORS) per launch and loops.  130 tensors that take the step
+    make three launches, tensors 64 and 128 the first of theirs (sizes 1025 and 1023: a vector body with a scalar tail); the list
+    also holds a zero-element tensor and one without gradient, which torch.optim.Adam and this class both pass over (placed last, so
+    that the k-th stepped tensor is the k-th parameter).  Ragged sizes around the 1024 elements of a workgroup; two steps."""
+    import nerf
+    g = torch.Generator().manual_seed(64)
+    sizes = [1, 3, 1023, 1024, 1025] + [int(n) for n in torch.randint(1, 3000, (125,), generator=g)]
+    sizes[64], sizes[128] = 1025, 1023
+    sizes += [0, 77]                                                    # the empty tensor; the tensor without gradient
+    assert len(sizes) == 132 and sum(n > 0 for n in sizes[:-1]) == 130
+    base = [torch.randn(n, generator=g) * 0.1 for n in sizes]
+    mk = lambda: [torch.nn.Parameter(b.clone().to(gpu)) for b in base]
+    pa, pb = mk(), mk()
+    oa, ob = nerf.optim.Adam(pa, lr=5e-4), torch.optim.Adam(pb, lr=5e-4)
+    for it in range(2):
+        for k, (a, b) in enumerate(zip(pa, pb)):
+            if k == len(sizes) - 1:
+                continue
+            gr = (torch.randn(sizes[k], generator=g) * (10.0 ** -(k % 4))).to(gpu)
+            a.grad, b.grad = gr.clone(), gr.clone()
+        oa.step()
+        ob.step()
+    for k, (a, b) in enumerate(zip(pa, pb)):
+        if sizes[k] == 0:
+            continue
+        err = float((a - b).abs().max() / (b.abs().max() + 1e-12))
+        assert err < 2e-6, (k, sizes[k], err)
+        moved = float((a.detach().cpu() - base[k]).abs().max()) > 0
+        assert moved == (k != len(sizes) - 1), k                        # every stepped tensor moved, the one without gradient did not
+    assert float(oa.state[pa[0]]["step"]) == float(oa.state[pa[64]]["step"]) == float(oa.state[pa[128]]["step"]) == 2.0
+    assert len(oa.state[pa[-1]]) == 0
+
+
 def test_training_loss_equals_the_torch_expression(hip_lib, gpu):
     """nerf.training_loss (TR:355-387 in two launches) against the trainer's own torch expression on the device: value and the three
     gradients, with a fine map and without, a zero latent code (ATen's norm_backward gives 0 there), strided colour maps."""

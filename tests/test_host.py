@@ -487,6 +487,26 @@ def test_entry_points_reject_bad_arguments_before_touching_the_device(hip_lib):
     assert lib.nf_paper_bwd_workspace_floats(262144) == 585984384
 
 
+def test_python_size_limits_mirror_the_render_kernels(hip_lib):
+    """nerf/ops.py refuses sizes beyond the render kernels' compile-time limits by name, before a launch: its three numbers are the
+    #defines of csrc/nf_render.hip, the C entry points still answer NF_EINVAL one past each of them, and the messages name the limit."""
+    from nerf import ops
+    src = open(os.path.join(ROOT, "4d-facial-avatars_amd", "csrc", "nf_render.hip")).read()
+    define = lambda name: int(re.search(rf"^#define {name} (\d+)", src, re.M).group(1))
+    assert ops.MAX_BINS == define("NF_MAX_BINS") and ops.MAX_SORT == define("NF_MAX_SORT")
+    assert ops.MAX_BWD_SAMPLES == 64 * define("NF_MAX_CHUNKS")
+    one = ctypes.c_void_p(16)                                                   # never dereferenced: the size check comes first
+    assert hip_lib.nf_sample_pdf_ex(one, one, one, 0, 4, ops.MAX_BINS + 1, 8, one, None, None, None) == -22
+    assert hip_lib.nf_sort_rows(one, 4, ops.MAX_SORT + 1, one, None) == -22
+    assert hip_lib.nf_resample_merge(one, one, one, 0, 4, 513, 512, None, one, None) == -22
+    assert hip_lib.nf_volume_render_bwd(one, one, one, None, None, one, 4, ops.MAX_BWD_SAMPLES + 1, 0, one, None) == -22
+    ops.check_sample_counts(513, 511, True)
+    ops.check_sample_counts(4096, 0, False)                                     # the forward integrator takes any count
+    for args, name in (((513, 512, False), "NF_MAX_SORT = 1024"), ((514, 64, False), "NF_MAX_BINS = 512"), ((1025, 0, True), "NF_MAX_CHUNKS = 16")):
+        with pytest.raises(ValueError, match=name):
+            ops.check_sample_counts(*args)
+
+
 def test_launcher_host_helpers():
     """Pure host-side pieces of the launchers: the importance map of TR:230-239 (p = 0.9 inside the bounding box, normalised) and
     the jet colour map of the error image (matplotlib's piecewise-linear 'jet' at its anchor points)."""
