@@ -98,6 +98,22 @@ _PROTOTYPES = {
     "nf_lcode_grad_floats": (_Z, []),
     "nf_lcode_bwd_workspace_floats": (_Z, [_L]),
     "nf_lcode_mlp_bwd": (C.c_int, [_P, _P, _P, _P, _P, _L, _I, _P, _Z, _P, _P]),
+    "nf_smaller_packed_floats": (_Z, []),
+    "nf_smaller_cond_floats": (_Z, []),
+    "nf_smaller_gather_table": (C.c_int, [_P, _Z]),
+    "nf_smaller_pack": (C.c_int, [_P, _P, _P]),
+    "nf_smaller_condition": (C.c_int, [_P, _P, _P, _F, _F, _P, _P]),
+    "nf_smaller_mlp_fwd": (C.c_int, [_P, _P, _P, _P, _P, _P, _L, _I, _P, _P]),
+    "nf_smaller_forward_encoded": (C.c_int, [_P, _P, _P, _P, _L, _P, _P, _P]),
+    "nf_smaller_saved_floats": (_Z, [_L]),
+    "nf_smaller_mlp_fwd_train": (C.c_int, [_P, _P, _P, _P, _P, _P, _L, _I, _P, _P, _P]),
+    "nf_smaller_packed_bwd_floats": (_Z, []),
+    "nf_smaller_pack_bwd": (C.c_int, [_P, _P, _P]),
+    "nf_smaller_grad_floats": (_Z, []),
+    "nf_smaller_bwd_workspace_floats": (_Z, [_L]),
+    "nf_smaller_mlp_bwd": (C.c_int, [_P, _P, _P, _P, _P, _L, _I, _P, _Z, _P, _P]),
+    "nf_smaller_mlp_bwd_stage_ms": (C.c_int, [_P, _P, _P, _P, _P, _L, _I, _P, _Z, _P, _P, _P]),
+    "nf_selftest_dw_tables_smaller_f32": (C.c_int, []),
     "nf_eval_postprocess": (C.c_int, [_P, _P, _P, _I, _I, _F, _F, _F, _F, _P, _P, _P]),
     "nf_tiny_packed_floats": (_Z, []),
     "nf_tiny_pack": (C.c_int, [_P, _P, _P]),

@@ -11,7 +11,7 @@ from __future__ import annotations
 import torch
 
 from . import ops
-from .ops import LCODE_KEYS  # noqa: F401  (parameter order of the second family, as include/nerface_hip.h names it)
+from .ops import LCODE_KEYS, SMALLER_KEYS  # noqa: F401  (parameter orders of the other families, as include/nerface_hip.h names them)
 
 
 class _FusedNeRFModel(torch.nn.Module):
@@ -36,6 +36,7 @@ class _FusedNeRFModel(torch.nn.Module):
         (None when no gradient is wanted)."""
         ops.check_conditioning(expr, latent)
         fam, hw, prec = self.FAMILY, self.hip_weights(), ops.get_mlp_precision()
+        fam.require_precision(prec)
         packed = hw.get()
         cond = ops.mlp_condition(fam, packed, expr, latent, near, far)
         if need_grad:
@@ -57,7 +58,7 @@ class _FusedNeRFModel(torch.nn.Module):
         return ops.mlp_bwd(self.FAMILY, self.hip_weights(), packed, cond, z, d_raw, saved, split=split)
 
     def forward(self, x, expr=None, latent_code=None, **kwargs):
-        """The reference's forward (paper model M:236-261, second family M:590-636) on pre-encoded inputs x (N, 87) =
+        """The reference's forward (paper model M:236-261, second family M:590-636, smaller paper model M:313-338) on pre-encoded inputs x (N, 87) =
         [PE10(xyz) | PE4(dirs)] -> (N, 4), as run_network calls it (T:9-33).  Inference only (kernel <prefix>_forward_encoded);
         training goes through run_one_iter_of_nerf, whose fused kernels own the backward."""
         if not self.fused_supported() or expr is None or latent_code is None:
@@ -156,6 +157,52 @@ class ConditionalBlendshapeLearnableCodeNeRFModel(_FusedNeRFModel):
         return (self.use_viewdirs and self.dim_xyz == 63 and self.dim_dir == 24 and self.dim_expression == 76
                 and self.dim_latent_code == 32 and self.layer1.out_features == 256 and len(self.layers_xyz) == 3
                 and all(l.in_features == 256 for l in self.layers_xyz))
+
+
+class ConditionalBlendshapePaperSmallerNeRFModel(_FusedNeRFModel):
+    r"""The paper model made smaller (reference nerf/models.py:266-338; the `ji` "smaller paper model" configs): the model a user
+    picks to trade quality for speed.
+
+    x0 = [PE10(xyz) (63) | expression*1/3 (76) | latent code (32)] -> 3 x (Linear 256 + ReLU) -> [x0 | h] -> 2 x (Linear 256 + ReLU)
+    -> feat = fc_feat(h) -> sigma = fc_alpha(feat); [feat | PE4(dir) (24) | expression*1/3 (76)] -> 3 x (Linear 128 + ReLU) ->
+    rgb = fc_rgb.  Against the paper model: no layers_xyz.5, no dead layers_dir.3, the expression a second time in front of the
+    colour branch; 22 tensors, 496,132 parameters, all live.  Constructor signature, parameter names, shapes and default
+    initialisation are the reference's, so its checkpoints load unchanged; num_layers / hidden_size / skip_connect_every are
+    accepted and ignored exactly as there.  Exact f32 only: under another nerf.set_mlp_precision it raises NotImplementedError.
+    """
+
+    FAMILY = ops.SMALLER
+
+    def __init__(self, num_layers=8, hidden_size=256, skip_connect_every=4, num_encoding_fn_xyz=6, num_encoding_fn_dir=4,
+                 include_input_xyz=True, include_input_dir=True, use_viewdirs=True, include_expression=True,
+                 latent_code_dim=32):
+        super().__init__()
+        include_input_xyz = 3 if include_input_xyz else 0
+        include_input_dir = 3 if include_input_dir else 0
+        include_expression = 76 if include_expression else 0
+        self.dim_xyz = include_input_xyz + 2 * 3 * num_encoding_fn_xyz
+        self.dim_dir = include_input_dir + 2 * 3 * num_encoding_fn_dir
+        self.dim_expression = include_expression
+        self.dim_latent_code = latent_code_dim
+        self.layers_xyz = torch.nn.ModuleList()
+        self.use_viewdirs = use_viewdirs
+        d_in = self.dim_xyz + self.dim_expression + self.dim_latent_code
+        self.layers_xyz.append(torch.nn.Linear(d_in, 256))
+        for i in range(1, 5):
+            self.layers_xyz.append(torch.nn.Linear(d_in + 256 if i == 3 else 256, 256))
+        self.fc_feat = torch.nn.Linear(256, 256)
+        self.fc_alpha = torch.nn.Linear(256, 1)
+        self.layers_dir = torch.nn.ModuleList()
+        self.layers_dir.append(torch.nn.Linear(256 + self.dim_dir + self.dim_expression, 128))
+        for _ in range(2):
+            self.layers_dir.append(torch.nn.Linear(128, 128))
+        self.fc_rgb = torch.nn.Linear(128, 3)
+        self.relu = torch.nn.functional.relu
+
+    def fused_supported(self) -> bool:
+        """The HIP kernels are specialised to the geometry of the configs that use this class."""
+        return (self.dim_xyz == 63 and self.dim_dir == 24 and self.dim_expression == 76 and self.dim_latent_code == 32
+                and self.use_viewdirs)
 
 
 class FlexibleNeRFModel(torch.nn.Module):

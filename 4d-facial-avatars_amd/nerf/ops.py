@@ -24,6 +24,8 @@ PAPER_KEYS = (
 )
 LCODE_KEYS = [f"{n}.{p}" for n in ("layer1", "layers_xyz.0", "layers_xyz.1", "layers_xyz.2", "layers_dir.0", "fc_alpha", "fc_rgb", "fc_feat")
               for p in ("weight", "bias")]
+SMALLER_KEYS = [f"{n}.{p}" for n in ([f"layers_xyz.{i}" for i in range(5)] + ["fc_feat", "fc_alpha"] + [f"layers_dir.{i}" for i in range(3)]
+                                     + ["fc_rgb"]) for p in ("weight", "bias")]
 
 
 # Arithmetic of the MLP GEMMs: "f32" = exact-f32 MFMA (the library default and the arithmetic of the reference);
@@ -194,13 +196,20 @@ def posenc(x: torch.Tensor, n_freq: int, include_input: bool) -> torch.Tensor:
 
 # ---------------------------------------------------------------------------------------- K4
 class MLPFamily(NamedTuple):
-    """What tells the two fused NeRFace MLP families apart.  Every entry point of a family is `<prefix>_<name>`, with one C
-    signature per name for both families (include/nerface_hip.h)."""
-    prefix: str                 # "nf_paper" / "nf_lcode"
+    """What tells the fused NeRFace MLP families apart.  Every entry point of a family is `<prefix>_<name>`, with one C
+    signature per name for all families (include/nerface_hip.h)."""
+    prefix: str                 # "nf_paper" / "nf_lcode" / "nf_smaller"
     keys: tuple                 # parameter names, in the order of the ABI's parameter-pointer arrays and gradient images
     hidden: tuple               # [lo, hi) of the hidden-activation sections of the exact-f32 `saved` buffer, in floats per point
     none_grads: tuple           # gradient slots autograd leaves None
     exact_dw: bool              # the split-bf16 backward takes (exact_dw, saved_f32)
+    precisions: tuple = _VALID_PRECISIONS   # the arithmetics of nerf.set_mlp_precision the family has kernels for
+
+    def require_precision(self, precision: str) -> None:
+        """A family without kernels for `precision` refuses it by name -- before anything is packed or launched."""
+        if precision not in self.precisions:
+            raise NotImplementedError(f'the {self.prefix} model family has no "{precision}" kernels (it serves '
+                                      f'{", ".join(repr(p) for p in self.precisions)}): use nerf.set_mlp_precision("f32")')
 
     def fn(self, name: str):
         return getattr(H.lib(), f"{self.prefix}_{name}")
@@ -217,6 +226,10 @@ PAPER = MLPFamily("nf_paper", tuple(PAPER_KEYS),
 LCODE = MLPFamily("nf_lcode", tuple(LCODE_KEYS),
                   (64, 1472),           # S_L1 .. S_DIRF (csrc/nf_mlp_lcode_layout.h): layer1, layers_xyz.0 .. 2, fc_feat, layers_dir.0
                   (), False)
+SMALLER = MLPFamily("nf_smaller", tuple(SMALLER_KEYS),
+                    (64, 1984),         # S_H0 .. S_DIRF (csrc/nf_mlp_smaller_layout.h): h0 .. h4, fc_feat, layers_dir.0 .. 2
+                    (), False,
+                    ("f32",))           # exact f32 only: the split arithmetics are not built for this family
 
 # Packed weight images are cached per (parameter storage, version counter, PACK EPOCH).  The version counter follows ordinary
 # in-place updates (optimizer.step() of the default / foreach optimizers, load_state_dict, copy_ under no_grad) -- but NOT every

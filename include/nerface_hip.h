@@ -266,6 +266,38 @@ int nf_lcode_mlp_bwd_bf16(const float* packed, const void* packed_t_bf16, const 
                           const float* d_raw, int64_t n_rays, int n_samples, float* workspace, size_t workspace_floats,
                           float* grads, nf_stream_t stream);
 
+/* ---- third model family: ConditionalBlendshapePaperSmallerNeRFModel (M:266-338) + run_network (T:9-33) -- the paper model without
+ * layers_xyz.5 and layers_dir.3, with layers_dir.0 reading [feat 256 | PE4(dir) 24 | expr/3 76].  EXACT F32 ONLY (no split
+ * arithmetics).  params: HOST array of 22 device pointers in state_dict order (layers_xyz.0..4, fc_feat, fc_alpha, layers_dir.0..2,
+ * fc_rgb; weight then bias).  Every nf_smaller_* entry point has the signature and the argument meaning of its nf_paper_*
+ * namesake; additive to ABI 5.  nf_smaller_condition also folds the 76 expression columns of layers_dir.0 into its bias.
+ * grads (nf_smaller_grad_floats()): the 22 tensors in state_dict order, flattened, then d latent (32); no tensor is dead.      */
+size_t nf_smaller_packed_floats(void);
+size_t nf_smaller_cond_floats(void);
+int nf_smaller_gather_table(uint32_t* out, size_t n /* must equal nf_smaller_packed_floats() */);
+int nf_smaller_pack(const float* const* params, float* packed, nf_stream_t stream);
+int nf_smaller_condition(const float* packed, const float* expr76, const float* latent32, float near_z, float far_z,
+                         float* cond, nf_stream_t stream);
+int nf_smaller_mlp_fwd(const float* packed, const float* cond, const float* ro, const float* rd, const float* rd_view,
+                       const float* z, int64_t n_rays, int n_samples, float* raw, nf_stream_t stream);
+int nf_smaller_forward_encoded(const float* packed, const float* x87, const float* expr76, const float* latent32,
+                               int64_t n_points, float* cond, float* out, nf_stream_t stream);
+size_t nf_smaller_saved_floats(int64_t n_points);
+int nf_smaller_mlp_fwd_train(const float* packed, const float* cond, const float* ro, const float* rd, const float* rd_view,
+                             const float* z, int64_t n_rays, int n_samples, float* raw, float* saved, nf_stream_t stream);
+size_t nf_smaller_packed_bwd_floats(void);
+int nf_smaller_pack_bwd(const float* const* params, float* packed_t, nf_stream_t stream);
+size_t nf_smaller_grad_floats(void);
+size_t nf_smaller_bwd_workspace_floats(int64_t n_points);
+int nf_smaller_mlp_bwd(const float* packed, const float* packed_t, const float* cond, const float* saved, const float* d_raw,
+                       int64_t n_rays, int n_samples, float* workspace, size_t workspace_floats, float* grads,
+                       nf_stream_t stream);
+/* Measurement hook (tools/time_smaller.py): one exact-f32 backward with HIP events between its stages; synchronises the stream;
+ * stage_ms[3] (host) = {dX chain, weight-gradient GEMMs, slab reduction + unpack} in milliseconds.                           */
+int nf_smaller_mlp_bwd_stage_ms(const float* packed, const float* packed_t, const float* cond, const float* saved,
+                                const float* d_raw, int64_t n_rays, int n_samples, float* workspace, size_t workspace_floats,
+                                float* grads, float* stage_ms, nf_stream_t stream);
+
 /* ---- BASELINE config 1: tiny_nerf.py (reference tiny_nerf.py:12-181) ----------------------------------------------
  * nf_tiny_mlp_fwd = compute_query_points_from_rays' pts = ro + rd*depth (tiny_nerf.py:59-63) + positional_encoding(., 10)
  * + VeryTinyNerfModel.forward (63 -> 128 -> 128 -> 4).  params: HOST array of 6 device pointers
@@ -402,6 +434,7 @@ int nf_sort_rows(const float* in, int64_t n_rows, int n_cols, float* out, nf_str
  * exactly once per slice, tile ids inside their bundle.  0 = consistent, negative = which check failed.                 */
 int nf_selftest_dw_tables_f32(void);
 int nf_selftest_dw_tables_lcode_f32(void);
+int nf_selftest_dw_tables_smaller_f32(void);
 int nf_selftest_dw_tables_bf16(void);
 int nf_selftest_dw_tables_tiny(void);
 int nf_selftest_dw_tables_flex(int num_layers);
