@@ -14,8 +14,10 @@
 
 
 
-static void nf_lcode_table(std::vector<uint32_t>& t) {
+// gather table of the exact-f32 image for a class of geometry `ge` (nf_mlp_lcode_layout.h)
+void nf_lcode_build_table(std::vector<uint32_t>& t, const NfLcodeGeom& ge) {
     using namespace nlc;
+    const int* id = ge.id;
     t.assign(PACKED, NF_ZERO_CODE);
     auto fill = [&](int off, int nk, int no_tiles, int tensor, int n_out, int n_cols, auto col_of) {
         nf_fill_frag(t, off, nk, no_tiles, [&](int slot, int n) {
@@ -24,32 +26,34 @@ static void nf_lcode_table(std::vector<uint32_t>& t) {
         });
     };
     auto ident = [](int s) { return s; };
-    fill(OFF_L1, 4, 16, 0, 256, 171, [](int s) { return nfl::pe_slot_to_col(s); });
-    fill(OFF_X0, 16, 16, 2, 256, 256, ident);
-    fill(OFF_X1, 16, 16, 4, 256, 256, ident);
-    fill(OFF_X2, 16, 16, 6, 256, 256, ident);
-    fill(OFF_ALPHA, 16, 1, 10, 1, 256, ident);
-    fill(OFF_FEAT, 16, 16, 14, 256, 256, ident);
-    fill(OFF_DIR, 17, 8, 8, 128, 280, [](int s) {
+    fill(OFF_L1, 4, 16, id[0], 256, ge.ld1, [](int s) { return nfl::pe_slot_to_col(s); });
+    fill(OFF_X0, 16, 16, id[2], 256, 256, ident);
+    fill(OFF_X1, 16, 16, id[4], 256, 256, ident);
+    fill(OFF_X2, 16, 16, id[6], 256, 256, ident);
+    fill(OFF_ALPHA, 16, 1, id[10], 1, 256, ident);
+    fill(OFF_FEAT, 16, 16, id[14], 256, 256, ident);
+    fill(OFF_DIR, 17, 8, id[8], 128, 280, [](int s) {
         if (s < 256) return s;
         const int g = ((s - 256) >> 2) & 3, r = (s - 256) & 3;
         return r < 2 ? 256 + 6 * g + 3 * r : -1;
     });
-    fill(OFF_RGB, 8, 1, 12, 3, 128, ident);
-    fill(OFF_DIRE, 18, 8, 8, 128, 280, [](int s) { return s < 280 ? s : -1; });
+    fill(OFF_RGB, 8, 1, id[12], 3, 128, ident);
+    fill(OFF_DIRE, 18, 8, id[8], 128, 280, [](int s) { return s < 280 ? s : -1; });
     for (int n = 0; n < 256; ++n)
-        for (int k = 0; k < 108; ++k) t[OFF_WC1 + n * 108 + k] = nf_code(0, n, 63 + k, 171);
+        for (int k = 0; k < ge.n_cond; ++k) t[OFF_WC1 + n * 108 + k] = nf_code(id[0], n, 63 + k, ge.ld1);
     for (int n = 0; n < 128; ++n)
         for (int f = 0; f < 4; ++f)
             for (int sc = 0; sc < 2; ++sc)
-                for (int comp = 1; comp < 3; ++comp) t[OFF_WCD + n * 16 + 4 * f + 2 * sc + (comp - 1)] = nf_code(8, n, 256 + 6 * f + 3 * sc + comp, 280);
+                for (int comp = 1; comp < 3; ++comp) t[OFF_WCD + n * 16 + 4 * f + 2 * sc + (comp - 1)] = nf_code(id[8], n, 256 + 6 * f + 3 * sc + comp, 280);
     const int b256[5] = {1, 3, 5, 7, 15};          // layer1, layers_xyz.0..2, fc_feat biases
     for (int l = 0; l < 5; ++l)
-        for (int n = 0; n < 256; ++n) t[OFF_BIAS + 256 * l + n] = nf_code(b256[l], 0, n, 256);
-    t[OFF_BIAS + B_ALPHA] = nf_code(11, 0, 0, 1);
-    for (int n = 0; n < 128; ++n) t[OFF_BIAS + B_DIR + n] = nf_code(9, 0, n, 128);
-    for (int n = 0; n < 3; ++n) t[OFF_BIAS + B_RGB + n] = nf_code(13, 0, n, 3);
+        for (int n = 0; n < 256; ++n) t[OFF_BIAS + 256 * l + n] = nf_code(id[b256[l]], 0, n, 256);
+    t[OFF_BIAS + B_ALPHA] = nf_code(id[11], 0, 0, 1);
+    for (int n = 0; n < 128; ++n) t[OFF_BIAS + B_DIR + n] = nf_code(id[9], 0, n, 128);
+    for (int n = 0; n < 3; ++n) t[OFF_BIAS + B_RGB + n] = nf_code(id[13], 0, n, 3);
 }
+
+static void nf_lcode_table(std::vector<uint32_t>& t) { nf_lcode_build_table(t, NF_LCODE_GEOM); }
 
 static NfPackTable g_lcode_table;
 
@@ -318,6 +322,8 @@ k_lcode_mlp_fwd_encoded(const float* __restrict__ packed, const float* __restric
     }
 }
 
+int nf_lcode_launch_fwd_encoded(const float* packed, const float* cond, const float* x87, int64_t n_points, float* out, nf_stream_t stream);
+
 // x87: (n_points, 87) pre-encoded inputs; cond: scratch of nf_lcode_cond_floats() floats; out: (n_points, 4).
 extern "C" int nf_lcode_forward_encoded(const float* packed, const float* x87, const float* expr76, const float* latent32,
                                         int64_t n_points, float* cond, float* out, nf_stream_t stream) {
@@ -325,6 +331,11 @@ extern "C" int nf_lcode_forward_encoded(const float* packed, const float* x87, c
     if (!packed || !x87 || !expr76 || !latent32 || !cond || !out || n_points < 0) return NF_EINVAL;
     hipLaunchKernelGGL(k_lcode_condition_encoded, dim3((nlc::COND_FLOATS + 255) / 256), dim3(256), 0, nf_s(stream), packed, expr76,
                        latent32, cond);
+    return nf_lcode_launch_fwd_encoded(packed, cond, x87, n_points, out, stream);
+}
+
+// k_lcode_mlp_fwd_encoded on a bias table that is already filled (also the classes of nf_mlp_bshape.hip / nf_mlp_cbshape.hip)
+int nf_lcode_launch_fwd_encoded(const float* packed, const float* cond, const float* x87, int64_t n_points, float* out, nf_stream_t stream) {
     constexpr int NT = NF_MLP_NT;
     const int64_t per_block = (int64_t)NF_MLP_WAVES * 16 * NT;
     const int64_t grid = (n_points + per_block - 1) / per_block;

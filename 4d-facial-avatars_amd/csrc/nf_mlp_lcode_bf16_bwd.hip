@@ -34,8 +34,11 @@ constexpr int STREAM_BF16 = N_PAIRS * 2 * 512;
 // transposed (hi, lo) stream: block (s, nt), lane (h', i), j  ->  W[row = reduction feature(s, h', j)][col = 32 nt + i]
 // =================================================================================================
 
-static void nf_lcode_table_bf16_t(std::vector<uint32_t>& t) {
+void nf_lcode_build_table_bf16_t(std::vector<uint32_t>& t, const NfLcodeGeom& ge);
+#if !NFB_F16       // one definition: this file is compiled a second time as nf_mlp_lcode_f16_bwd.hip
+void nf_lcode_build_table_bf16_t(std::vector<uint32_t>& t, const NfLcodeGeom& ge) {
     using namespace nfb;
+    const int* id = ge.id;
     t.assign((size_t)N_PAIRS * 512, NF_ZERO_CODE);
     for (int l = 0; l < NL; ++l)
         for (int s = 0; s < KS[l]; ++s)
@@ -45,19 +48,27 @@ static void nf_lcode_table_bf16_t(std::vector<uint32_t>& t) {
                         const int h = lane >> 5, i = lane & 31, col = 32 * nt + i, row = hid_feature(s, h, j);
                         uint32_t c = NF_ZERO_CODE;
                         switch (l) {
-                            case 0: if (s == 0 && h == 0 && j < 3) c = nf_code(12, j, col, 128); break;      // slots 0..2 carry d r, d g, d b
-                            case 1: if (row < 128) c = nf_code(8, row, col, 280); break;
+                            case 0: if (s == 0 && h == 0 && j < 3) c = nf_code(id[12], j, col, 128); break;      // slots 0..2 carry d r, d g, d b
+                            case 1: if (row < 128) c = nf_code(id[8], row, col, 280); break;
                             case 2:                                                                      // k-step 16, slot (0, 0): d sigma
-                                if (s < 16) c = nf_code(14, row, col, 256);
-                                else if (s == 16 && h == 0 && j == 0) c = nf_code(10, 0, col, 256);
+                                if (s < 16) c = nf_code(id[14], row, col, 256);
+                                else if (s == 16 && h == 0 && j == 0) c = nf_code(id[10], 0, col, 256);
                                 break;
-                            case 3: c = nf_code(6, row, col, 256); break;
-                            case 4: c = nf_code(4, row, col, 256); break;
-                            case 5: c = nf_code(2, row, col, 256); break;
+                            case 3: c = nf_code(id[6], row, col, 256); break;
+                            case 4: c = nf_code(id[4], row, col, 256); break;
+                            case 5: c = nf_code(id[2], row, col, 256); break;
                         }
                         t[((size_t)(pair_off(l) + s * NO[l] + nt)) * 512 + lane * 8 + j] = c;
                     }
 }
+#else
+// layer boundaries (NL + 1 pair offsets) of the transposed stream, for the classes that pack their own tensors into it
+void nf_lcode_bwd_f16_stream_layers(int* pair_off) {
+    for (int l = 0; l <= nfb::NL; ++l) pair_off[l] = nfb::pair_off(l);
+}
+#endif
+
+static void nf_lcode_table_bf16_t(std::vector<uint32_t>& t) { nf_lcode_build_table_bf16_t(t, NF_LCODE_GEOM); }
 
 static NfPackTable g_lcode_table_bt;
 

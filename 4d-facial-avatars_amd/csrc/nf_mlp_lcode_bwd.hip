@@ -18,18 +18,21 @@
 // =================================================================================================
 // transposed pack: block (ni, no), lane (g, i), r -> W[row = 16 ni + 4 g + r][col = 16 no + i]
 // =================================================================================================
-static void nf_lcode_table_t(std::vector<uint32_t>& t) {
+void nf_lcode_build_table_t(std::vector<uint32_t>& t, const NfLcodeGeom& ge) {
     using namespace nlc;
+    const int* id = ge.id;
     t.assign(PACKED_T, NF_ZERO_CODE);
     auto fill = [&](int off, int nk, int no_tiles, int tensor, int n_rows, int n_cols) { nf_fill_frag_t(t, off, nk, no_tiles, tensor, n_rows, n_cols); };
-    fill(OFFT_RGB, 1, 8, 12, 3, 128);                       // fc_rgb.weight (3, 128)
-    fill(OFFT_DIR, 8, 16, 8, 128, 280);                     // layers_dir.0.weight[:, :256]
-    fill(OFFT_FEAT, 16, 16, 14, 256, 256);                  // fc_feat.weight
-    fill(OFFT_FEAT + 16 * 16 * FRAG, 1, 16, 10, 1, 256);    // chunk 16, slot 0: fc_alpha.weight (1, 256)
-    fill(OFFT_X2, 16, 16, 6, 256, 256);
-    fill(OFFT_X1, 16, 16, 4, 256, 256);
-    fill(OFFT_X0, 16, 16, 2, 256, 256);
+    fill(OFFT_RGB, 1, 8, id[12], 3, 128);                       // fc_rgb.weight (3, 128)
+    fill(OFFT_DIR, 8, 16, id[8], 128, 280);                     // layers_dir.0.weight[:, :256]
+    fill(OFFT_FEAT, 16, 16, id[14], 256, 256);                  // fc_feat.weight
+    fill(OFFT_FEAT + 16 * 16 * FRAG, 1, 16, id[10], 1, 256);    // chunk 16, slot 0: fc_alpha.weight (1, 256)
+    fill(OFFT_X2, 16, 16, id[6], 256, 256);
+    fill(OFFT_X1, 16, 16, id[4], 256, 256);
+    fill(OFFT_X0, 16, 16, id[2], 256, 256);
 }
+
+static void nf_lcode_table_t(std::vector<uint32_t>& t) { nf_lcode_build_table_t(t, NF_LCODE_GEOM); }
 
 static NfPackTable g_lcode_table_t;
 
@@ -299,6 +302,18 @@ static const NfBwdFamily nf_lcode_bwd = {1, nlc::DZ_PER_POINT, nlc::SLAB_FLOATS,
                                          {nf_lcode_chain_f32, nfb_lcode_launch_bwd_chain_bf16, nfb_lcode_launch_bwd_chain_f16},
                                          nf_lcode_dw_f32, nf_lcode_reduce_unpack};
 
+// the same record with another scatter kernel behind the slab reduction: the classes of nf_mlp_bshape.hip / nf_mlp_cbshape.hip
+void nf_lcode_grad_reduce(const float* slabs, int ns, const NfReduceAlt& alt, float* sum, hipStream_t s) {
+    hipLaunchKernelGGL((k_grad_reduce<1>), dim3(512), dim3(256), 0, s, slabs, ns, (int)nlc::SLAB_FLOATS, sum, alt);
+}
+
+NfBwdFamily nf_lcode_bwd_family(void (*reduce_unpack)(const float*, int, const NfReduceAlt&, float*, const float*, const float*, float*,
+                                                      hipStream_t)) {
+    NfBwdFamily fam = nf_lcode_bwd;
+    fam.reduce_unpack = reduce_unpack;
+    return fam;
+}
+
 extern "C" size_t nf_lcode_bwd_workspace_floats(int64_t n_points) { return nf_bwd_workspace_floats(nf_lcode_bwd, n_points); }
 
 extern "C" int nf_lcode_mlp_bwd(const float* packed, const float* packed_t, const float* cond, const float* saved, const float* d_raw,
@@ -322,6 +337,16 @@ extern "C" int nf_lcode_mlp_bwd_f16(const float* packed, const void* packed_t_f1
                                     float* grads, nf_stream_t stream) {
     return nf_bwd_run(nf_lcode_bwd, 2, packed, packed_t_f16, cond, saved, d_raw, n_rays, n_samples, workspace, workspace_floats, grads,
                       stream);
+}
+
+// Measurement hook (tools/time_blendshape.py), as nf_paper_mlp_bwd_stage_ms: one backward in arithmetic `precision` (0 exact f32, 1 split-bf16,
+// 2 split-fp16; packed_t_any: the matching transposed image / stream) with HIP events between its stages; synchronises the stream.
+extern "C" int nf_lcode_mlp_bwd_stage_ms(const float* packed, const void* packed_t_any, int precision, const float* cond, const float* saved,
+                                         const float* d_raw, int64_t n_rays, int n_samples, float* workspace, size_t workspace_floats,
+                                         float* grads, float* stage_ms, nf_stream_t stream) {
+    if (precision < 0 || precision > 2 || !stage_ms) return NF_EINVAL;
+    return nf_bwd_run(nf_lcode_bwd, precision, packed, packed_t_any, cond, saved, d_raw, n_rays, n_samples, workspace, workspace_floats, grads,
+                      stream, stage_ms);
 }
 
 // host-only self-test of this family's exact-f32 group table (tests/test_host.py)

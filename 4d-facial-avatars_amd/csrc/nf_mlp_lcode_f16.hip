@@ -24,6 +24,12 @@ extern "C" int nf_lcode_pack_f16(const float* const* params, void* stream_out, n
                                               (float)(1 << NFB_ACT_SHIFT), stream);
 }
 
+// the stream's layer boundaries (NL + 1 pair offsets) and activation pre-scale, for the classes that pack their own tensors into it
+float nf_lcode_f16_stream_layers(int* pair_off) {
+    for (int l = 0; l <= nfb::NL; ++l) pair_off[l] = nfb::pair_off(l);
+    return (float)(1 << NFB_ACT_SHIFT);
+}
+
 #define NFB_SAVE 0
 #define NFB_KERNEL_NAME k_lcode_mlp_fwd_f16
 #include "nf_mlp_lcode_bf16_kernel.inc"

@@ -64,3 +64,13 @@ constexpr int SLAB_FLOATS = CS_RGB + 16;
 constexpr int GRAD_PARAM_FLOATS = 256 * 171 + 256 + 3 * (65536 + 256) + 128 * 280 + 128 + 256 + 1 + 384 + 3 + 65536 + 256;
 constexpr int GRAD_FLOATS = GRAD_PARAM_FLOATS + 32;
 }  // namespace nlc
+
+// What tells apart the model classes that run on this family's per-point kernels (nf_mlp_bshape.hip, nf_mlp_cbshape.hip): where
+// the 16 trunk tensors (order above) sit in the class's parameter list, layer1.weight's leading dimension, and how many of
+// the 108 columns of the conditioning block OFF_WC1 the class has (the rest stay zero).  The gather-table builders take one.
+struct NfLcodeGeom {
+    int id[nlc::NPARAMS];
+    int ld1;
+    int n_cond;
+};
+static const NfLcodeGeom NF_LCODE_GEOM = {{0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15}, 171, 108};

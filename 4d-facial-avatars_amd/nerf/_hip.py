@@ -153,6 +153,31 @@ _PROTOTYPES = {
     "nf_train_loss_bwd": (C.c_int, [_P, _P, _P, _L, _P, _I, _F, _F, _P, _P, _P, _P, _P, _P]),
     "nf_sort_rows": (C.c_int, [_P, _L, _I, _P, _P]),
 }
+_FAMILY_ENTRY_POINTS = {          # <prefix>_<name> of a family with every arithmetic (the names nerf/ops.py calls), one signature per name
+    "packed_floats": (_Z, []), "cond_floats": (_Z, []), "pack": (C.c_int, [_P, _P, _P]),
+    "condition": (C.c_int, [_P, _P, _P, _F, _F, _P, _P]),
+    "mlp_fwd": (C.c_int, [_P, _P, _P, _P, _P, _P, _L, _I, _P, _P]), "mlp_fwd_bf16": (C.c_int, [_P, _P, _P, _P, _P, _P, _L, _I, _P, _P]),
+    "mlp_fwd_f16": (C.c_int, [_P, _P, _P, _P, _P, _P, _L, _I, _P, _P]), "mlp_fwd_f16x2": (C.c_int, [_P, _P, _P, _P, _P, _P, _L, _I, _P, _P]),
+    "saved_floats": (_Z, [_L]),
+    "mlp_fwd_train": (C.c_int, [_P, _P, _P, _P, _P, _P, _L, _I, _P, _P, _P]),
+    "mlp_fwd_train_bf16": (C.c_int, [_P, _P, _P, _P, _P, _P, _L, _I, _P, _P, _P]),
+    "mlp_fwd_train_f16": (C.c_int, [_P, _P, _P, _P, _P, _P, _L, _I, _P, _P, _P]),
+    "packed_bwd_floats": (_Z, []), "pack_bwd": (C.c_int, [_P, _P, _P]),
+    "packed_bf16_bytes": (_Z, []), "pack_bf16": (C.c_int, [_P, _P, _P]),
+    "packed_bwd_bf16_bytes": (_Z, []), "pack_bwd_bf16": (C.c_int, [_P, _P, _P]),
+    "packed_f16_bytes": (_Z, []), "pack_f16": (C.c_int, [_P, _P, _P]),
+    "packed_bwd_f16_bytes": (_Z, []), "pack_bwd_f16": (C.c_int, [_P, _P, _P]),
+    "f16_flag_offset": (_Z, []),
+    "bwd_workspace_floats": (_Z, [_L]), "grad_floats": (_Z, []),
+    "mlp_bwd": (C.c_int, [_P, _P, _P, _P, _P, _L, _I, _P, _Z, _P, _P]),
+    "mlp_bwd_bf16": (C.c_int, [_P, _P, _P, _P, _P, _L, _I, _P, _Z, _P, _P]),
+    "mlp_bwd_f16": (C.c_int, [_P, _P, _P, _P, _P, _L, _I, _P, _Z, _P, _P]),
+    "forward_encoded": (C.c_int, [_P, _P, _P, _P, _L, _P, _P, _P]),
+}
+for _prefix in ("nf_bshape", "nf_cbshape"):
+    _PROTOTYPES.update({f"{_prefix}_{_name}": _sig for _name, _sig in _FAMILY_ENTRY_POINTS.items()})
+for _prefix in ("nf_lcode", "nf_bshape", "nf_cbshape"):          # measurement hook (tools/time_blendshape.py)
+    _PROTOTYPES[f"{_prefix}_mlp_bwd_stage_ms"] = (C.c_int, [_P, _P, _I, _P, _P, _P, _L, _I, _P, _Z, _P, _P, _P])
 # entry points that later ABI revisions add; absent symbols only fail when called
 _OPTIONAL = set()
 # the revision of include/nerface_hip.h these prototypes were written for (nf_abi_version() of the library must equal it: a stale

@@ -11,7 +11,7 @@ from __future__ import annotations
 import torch
 
 from . import ops
-from .ops import LCODE_KEYS, SMALLER_KEYS  # noqa: F401  (parameter orders of the other families, as include/nerface_hip.h names them)
+from .ops import BSHAPE_KEYS, CBSHAPE_KEYS, LCODE_KEYS, SMALLER_KEYS  # noqa: F401  (parameter orders of the other families, as include/nerface_hip.h names them)
 
 
 class _FusedNeRFModel(torch.nn.Module):
@@ -19,6 +19,7 @@ class _FusedNeRFModel(torch.nn.Module):
     (FAMILY, an ops.MLPFamily) and says which geometries the kernels serve (fused_supported)."""
 
     FAMILY: ops.MLPFamily
+    NEEDS_LATENT = True           # forward() without latent_code raises (False: the class's reference forward ignores it)
 
     def hip_param_list(self):
         sd = dict(self.named_parameters())
@@ -61,8 +62,10 @@ class _FusedNeRFModel(torch.nn.Module):
         """The reference's forward (paper model M:236-261, second family M:590-636, smaller paper model M:313-338) on pre-encoded inputs x (N, 87) =
         [PE10(xyz) | PE4(dirs)] -> (N, 4), as run_network calls it (T:9-33).  Inference only (kernel <prefix>_forward_encoded);
         training goes through run_one_iter_of_nerf, whose fused kernels own the backward."""
-        if not self.fused_supported() or expr is None or latent_code is None:
+        if not self.fused_supported() or expr is None or (latent_code is None and self.NEEDS_LATENT):
             raise NotImplementedError("forward() is built for the NeRFace geometry and needs expr and latent_code")
+        if latent_code is None:                      # a class without a latent code (M:821, M:935): the kernels ignore it
+            latent_code = torch.zeros(32, dtype=torch.float32, device=x.device)
         if torch.is_grad_enabled() and (x.requires_grad or latent_code.requires_grad or any(p.requires_grad for p in self.parameters())):
             raise NotImplementedError(f"{type(self).__name__}.forward has no autograd on the MI355X build: train through "
                                       "nerf.run_one_iter_of_nerf(...), or call forward under torch.no_grad()")
@@ -157,6 +160,78 @@ class ConditionalBlendshapeLearnableCodeNeRFModel(_FusedNeRFModel):
         return (self.use_viewdirs and self.dim_xyz == 63 and self.dim_dir == 24 and self.dim_expression == 76
                 and self.dim_latent_code == 32 and self.layer1.out_features == 256 and len(self.layers_xyz) == 3
                 and all(l.in_features == 256 for l in self.layers_xyz))
+
+
+class _BlendshapeNoCodeNeRFModel(_FusedNeRFModel):
+    """What the two blendshape classes without a learnable code share: the second family's trunk behind a layer1 that reads
+    [PE(xyz) | conditioning vector].  The reference's constructor signature (no latent_code_dim), parameter names, shapes and
+    registration order.  A latent code handed to forward / hip_forward is accepted and ignored, as the reference does (it arrives in
+    **kwargs); its gradient from these models is zero -- only the trainer's regulariser (nerf.training_loss) moves it."""
+
+    NEEDS_LATENT = False
+    DIM_CONDITION: int            # columns of layer1.weight behind the 63 of PE(xyz)
+
+    def _build_trunk(self, num_layers, hidden_size, skip_connect_every, num_encoding_fn_xyz, num_encoding_fn_dir, include_input_xyz,
+                     include_input_dir, use_viewdirs):
+        self.dim_xyz = (3 if include_input_xyz else 0) + 2 * 3 * num_encoding_fn_xyz
+        self.dim_dir = (3 if include_input_dir else 0) + 2 * 3 * num_encoding_fn_dir if use_viewdirs else 0
+        self.skip_connect_every = skip_connect_every
+        self.layer1 = torch.nn.Linear(self.dim_xyz + self.dim_expression, hidden_size)
+        self.layers_xyz = torch.nn.ModuleList()
+        for i in range(num_layers - 1):
+            skip = i % self.skip_connect_every == 0 and i > 0 and i != num_layers - 1
+            self.layers_xyz.append(torch.nn.Linear(self.dim_xyz + hidden_size + self.dim_expression if skip else hidden_size, hidden_size))
+        self.use_viewdirs = use_viewdirs
+        if self.use_viewdirs:
+            self.layers_dir = torch.nn.ModuleList()
+            self.layers_dir.append(torch.nn.Linear(self.dim_dir + hidden_size, hidden_size // 2))
+            self.fc_alpha = torch.nn.Linear(hidden_size, 1)
+            self.fc_rgb = torch.nn.Linear(hidden_size // 2, 3)
+            self.fc_feat = torch.nn.Linear(hidden_size, hidden_size)
+        else:
+            self.fc_out = torch.nn.Linear(hidden_size, 4)
+        self.relu = torch.nn.functional.relu
+        self.sigmoid = torch.sigmoid
+
+    def fused_supported(self) -> bool:
+        return (self.use_viewdirs and self.dim_xyz == 63 and self.dim_dir == 24 and self.layer1.out_features == 256
+                and self.layer1.in_features == 63 + self.DIM_CONDITION and len(self.layers_xyz) == 3
+                and all(l.in_features == 256 for l in self.layers_xyz))
+
+
+class ConditionalCompressedBlendshapeNeRFModel(_BlendshapeNoCodeNeRFModel):
+    r"""Reference nerf/models.py:750-868 (the `*_nolcode_fixed_bg_256_compressed` configs, 6 entries): the expression goes through
+    layers_expr = Linear 76 -> 38 -> 20 -> 20 with a ReLU after EACH layer and without the division by 3 (M:832-834), and layer1
+    reads [PE10(xyz) (63) | e3 (20)]; behind it the second family's trunk.  dim_expression is 20 whatever include_expression says,
+    as in the reference (M:779).  22 tensors; every arithmetic of nerf.set_mlp_precision.  The encoder is evaluated once per call
+    on the device (nf_cbshape_condition) and trained by the backward of the same kernels' gradient scatter."""
+
+    FAMILY = ops.CBSHAPE
+    DIM_CONDITION = 20
+
+    def __init__(self, num_layers=4, hidden_size=128, skip_connect_every=4, num_encoding_fn_xyz=6, num_encoding_fn_dir=4,
+                 include_input_xyz=True, include_input_dir=True, use_viewdirs=True, include_expression=True):
+        super().__init__()
+        self.dim_expression = 20
+        self.layers_expr = torch.nn.ModuleList([torch.nn.Linear(76, 38), torch.nn.Linear(38, 20), torch.nn.Linear(20, 20)])
+        self._build_trunk(num_layers, hidden_size, skip_connect_every, num_encoding_fn_xyz, num_encoding_fn_dir, include_input_xyz,
+                          include_input_dir, use_viewdirs)
+
+
+class ConditionalBlendshapeNeRFModel(_BlendshapeNoCodeNeRFModel):
+    r"""Reference nerf/models.py:872-976 (`ji_nolcode_fixed_bg_256`, `..._train_cams`; 4 entries): the second family without the
+    latent code -- layer1 reads [PE10(xyz) (63) | expression*1/3 (76)].  16 tensors; every arithmetic of nerf.set_mlp_precision."""
+
+    FAMILY = ops.BSHAPE
+    DIM_CONDITION = 76
+
+    def __init__(self, num_layers=4, hidden_size=128, skip_connect_every=4, num_encoding_fn_xyz=6, num_encoding_fn_dir=4,
+                 include_input_xyz=True, include_input_dir=True, use_viewdirs=True, include_expression=True):
+        super().__init__()
+        self.dim_expression = 76 if include_expression else 0
+        self.layers_expr = None
+        self._build_trunk(num_layers, hidden_size, skip_connect_every, num_encoding_fn_xyz, num_encoding_fn_dir, include_input_xyz,
+                          include_input_dir, use_viewdirs)
 
 
 class ConditionalBlendshapePaperSmallerNeRFModel(_FusedNeRFModel):

@@ -26,6 +26,8 @@ LCODE_KEYS = [f"{n}.{p}" for n in ("layer1", "layers_xyz.0", "layers_xyz.1", "la
               for p in ("weight", "bias")]
 SMALLER_KEYS = [f"{n}.{p}" for n in ([f"layers_xyz.{i}" for i in range(5)] + ["fc_feat", "fc_alpha"] + [f"layers_dir.{i}" for i in range(3)]
                                      + ["fc_rgb"]) for p in ("weight", "bias")]
+BSHAPE_KEYS = list(LCODE_KEYS)                                                   # ConditionalBlendshapeNeRFModel: layer1.weight (256, 139)
+CBSHAPE_KEYS = [f"layers_expr.{i}.{p}" for i in range(3) for p in ("weight", "bias")] + LCODE_KEYS    # the compressed class: (256, 83)
 
 
 # Arithmetic of the MLP GEMMs: "f32" = exact-f32 MFMA (the library default and the arithmetic of the reference);
@@ -198,7 +200,7 @@ def posenc(x: torch.Tensor, n_freq: int, include_input: bool) -> torch.Tensor:
 class MLPFamily(NamedTuple):
     """What tells the fused NeRFace MLP families apart.  Every entry point of a family is `<prefix>_<name>`, with one C
     signature per name for all families (include/nerface_hip.h)."""
-    prefix: str                 # "nf_paper" / "nf_lcode" / "nf_smaller"
+    prefix: str                 # "nf_paper" / "nf_lcode" / "nf_smaller" / "nf_bshape" / "nf_cbshape"
     keys: tuple                 # parameter names, in the order of the ABI's parameter-pointer arrays and gradient images
     hidden: tuple               # [lo, hi) of the hidden-activation sections of the exact-f32 `saved` buffer, in floats per point
     none_grads: tuple           # gradient slots autograd leaves None
@@ -230,6 +232,11 @@ SMALLER = MLPFamily("nf_smaller", tuple(SMALLER_KEYS),
                     (64, 1984),         # S_H0 .. S_DIRF (csrc/nf_mlp_smaller_layout.h): h0 .. h4, fc_feat, layers_dir.0 .. 2
                     (), False,
                     ("f32",))           # exact f32 only: the split arithmetics are not built for this family
+
+# the two blendshape classes without a learnable code: the second family's per-point kernels and buffer layouts (so its `hidden`
+# range), their own pack tables, bias table and gradient scatter (csrc/nf_mlp_bshape.hip, csrc/nf_mlp_cbshape.hip)
+BSHAPE = MLPFamily("nf_bshape", tuple(BSHAPE_KEYS), LCODE.hidden, (), False)
+CBSHAPE = MLPFamily("nf_cbshape", tuple(CBSHAPE_KEYS), LCODE.hidden, (), False)
 
 # Packed weight images are cached per (parameter storage, version counter, PACK EPOCH).  The version counter follows ordinary
 # in-place updates (optimizer.step() of the default / foreach optimizers, load_state_dict, copy_ under no_grad) -- but NOT every

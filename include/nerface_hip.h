@@ -266,6 +266,113 @@ int nf_lcode_mlp_bwd_bf16(const float* packed, const void* packed_t_bf16, const 
                           const float* d_raw, int64_t n_rays, int n_samples, float* workspace, size_t workspace_floats,
                           float* grads, nf_stream_t stream);
 
+/* ---- the two blendshape classes without a learnable code, on the second family's per-point kernels (additive to ABI 5) ----------
+ * nf_bshape_*:  ConditionalBlendshapeNeRFModel (M:872-976): layer1 reads [PE 63 | expr/3 76].  params: HOST array of 16 device
+ *               pointers, the second family's order, layer1.weight (256, 139).
+ * nf_cbshape_*: ConditionalCompressedBlendshapeNeRFModel (M:750-868): layer1 reads [PE 63 | e3 20], e3 = the expression encoder
+ *               layers_expr (76 -> 38 -> 20 -> 20, a ReLU after each layer, expression not divided by 3), evaluated once per call by
+ *               nf_cbshape_condition.  params: HOST array of 22 device pointers in state_dict order (layers_expr.0..2, then the 16 of
+ *               the second family with layer1.weight (256, 83)); its packed f32 image carries the encoder behind the trunk image.
+ * Every entry point has the signature and the argument meaning of its nf_lcode_* namesake; images, `cond`, `saved` and the
+ * workspace have the second family's sizes (nf_cbshape_packed_floats() excepted).  latent32 is accepted and ignored (may be NULL).
+ * grads: the class's tensors in params order, flattened, then 32 zeros (d latent: neither class reads a latent code).            */
+size_t nf_bshape_packed_floats(void);
+size_t nf_bshape_cond_floats(void);
+int nf_bshape_pack(const float* const* params, float* packed, nf_stream_t stream);
+int nf_bshape_condition(const float* packed, const float* expr76, const float* latent32, float near_z, float far_z, float* cond,
+                    nf_stream_t stream);
+int nf_bshape_mlp_fwd(const float* packed, const float* cond, const float* ro, const float* rd, const float* rd_view, const float* z,
+                  int64_t n_rays, int n_samples, float* raw, nf_stream_t stream);
+int nf_bshape_forward_encoded(const float* packed, const float* x87, const float* expr76, const float* latent32, int64_t n_points,
+                          float* cond, float* out, nf_stream_t stream);
+size_t nf_bshape_packed_bf16_bytes(void);
+int nf_bshape_pack_bf16(const float* const* params, void* packed_bf16, nf_stream_t stream);
+int nf_bshape_mlp_fwd_bf16(const void* packed_bf16, const float* cond, const float* ro, const float* rd, const float* rd_view,
+                       const float* z, int64_t n_rays, int n_samples, float* raw, nf_stream_t stream);
+size_t nf_bshape_packed_f16_bytes(void);
+size_t nf_bshape_f16_flag_offset(void);
+int nf_bshape_pack_f16(const float* const* params, void* stream_out, nf_stream_t stream);
+int nf_bshape_mlp_fwd_f16(const void* packed_f16, const float* cond, const float* ro, const float* rd, const float* rd_view,
+                      const float* z, int64_t n_rays, int n_samples, float* raw, nf_stream_t stream);
+int nf_bshape_mlp_fwd_f16x2(const void* packed_f16, const float* cond, const float* ro, const float* rd, const float* rd_view,
+                        const float* z, int64_t n_rays, int n_samples, float* raw, nf_stream_t stream);
+size_t nf_bshape_saved_floats(int64_t n_points);
+int nf_bshape_mlp_fwd_train(const float* packed, const float* cond, const float* ro, const float* rd, const float* rd_view,
+                        const float* z, int64_t n_rays, int n_samples, float* raw, float* saved, nf_stream_t stream);
+int nf_bshape_mlp_fwd_train_bf16(const void* packed_bf16, const float* cond, const float* ro, const float* rd, const float* rd_view,
+                             const float* z, int64_t n_rays, int n_samples, float* raw, float* saved, nf_stream_t stream);
+int nf_bshape_mlp_fwd_train_f16(const void* packed_f16, const float* cond, const float* ro, const float* rd, const float* rd_view,
+                            const float* z, int64_t n_rays, int n_samples, float* raw, float* saved, nf_stream_t stream);
+size_t nf_bshape_packed_bwd_floats(void);
+int nf_bshape_pack_bwd(const float* const* params, float* packed_t, nf_stream_t stream);
+size_t nf_bshape_packed_bwd_bf16_bytes(void);
+int nf_bshape_pack_bwd_bf16(const float* const* params, void* packed_t_bf16, nf_stream_t stream);
+size_t nf_bshape_packed_bwd_f16_bytes(void);
+int nf_bshape_pack_bwd_f16(const float* const* params, void* stream_out, nf_stream_t stream);
+size_t nf_bshape_grad_floats(void);
+size_t nf_bshape_bwd_workspace_floats(int64_t n_points);
+int nf_bshape_mlp_bwd(const float* packed, const float* packed_t, const float* cond, const float* saved, const float* d_raw,
+                  int64_t n_rays, int n_samples, float* workspace, size_t workspace_floats, float* grads, nf_stream_t stream);
+int nf_bshape_mlp_bwd_bf16(const float* packed, const void* packed_t_bf16, const float* cond, const float* saved, const float* d_raw,
+                       int64_t n_rays, int n_samples, float* workspace, size_t workspace_floats, float* grads, nf_stream_t stream);
+int nf_bshape_mlp_bwd_f16(const float* packed, const void* packed_t_f16, const float* cond, const float* saved, const float* d_raw,
+                      int64_t n_rays, int n_samples, float* workspace, size_t workspace_floats, float* grads, nf_stream_t stream);
+
+size_t nf_cbshape_packed_floats(void);
+size_t nf_cbshape_cond_floats(void);
+int nf_cbshape_pack(const float* const* params, float* packed, nf_stream_t stream);
+int nf_cbshape_condition(const float* packed, const float* expr76, const float* latent32, float near_z, float far_z, float* cond,
+                    nf_stream_t stream);
+int nf_cbshape_mlp_fwd(const float* packed, const float* cond, const float* ro, const float* rd, const float* rd_view, const float* z,
+                  int64_t n_rays, int n_samples, float* raw, nf_stream_t stream);
+int nf_cbshape_forward_encoded(const float* packed, const float* x87, const float* expr76, const float* latent32, int64_t n_points,
+                          float* cond, float* out, nf_stream_t stream);
+size_t nf_cbshape_packed_bf16_bytes(void);
+int nf_cbshape_pack_bf16(const float* const* params, void* packed_bf16, nf_stream_t stream);
+int nf_cbshape_mlp_fwd_bf16(const void* packed_bf16, const float* cond, const float* ro, const float* rd, const float* rd_view,
+                       const float* z, int64_t n_rays, int n_samples, float* raw, nf_stream_t stream);
+size_t nf_cbshape_packed_f16_bytes(void);
+size_t nf_cbshape_f16_flag_offset(void);
+int nf_cbshape_pack_f16(const float* const* params, void* stream_out, nf_stream_t stream);
+int nf_cbshape_mlp_fwd_f16(const void* packed_f16, const float* cond, const float* ro, const float* rd, const float* rd_view,
+                      const float* z, int64_t n_rays, int n_samples, float* raw, nf_stream_t stream);
+int nf_cbshape_mlp_fwd_f16x2(const void* packed_f16, const float* cond, const float* ro, const float* rd, const float* rd_view,
+                        const float* z, int64_t n_rays, int n_samples, float* raw, nf_stream_t stream);
+size_t nf_cbshape_saved_floats(int64_t n_points);
+int nf_cbshape_mlp_fwd_train(const float* packed, const float* cond, const float* ro, const float* rd, const float* rd_view,
+                        const float* z, int64_t n_rays, int n_samples, float* raw, float* saved, nf_stream_t stream);
+int nf_cbshape_mlp_fwd_train_bf16(const void* packed_bf16, const float* cond, const float* ro, const float* rd, const float* rd_view,
+                             const float* z, int64_t n_rays, int n_samples, float* raw, float* saved, nf_stream_t stream);
+int nf_cbshape_mlp_fwd_train_f16(const void* packed_f16, const float* cond, const float* ro, const float* rd, const float* rd_view,
+                            const float* z, int64_t n_rays, int n_samples, float* raw, float* saved, nf_stream_t stream);
+size_t nf_cbshape_packed_bwd_floats(void);
+int nf_cbshape_pack_bwd(const float* const* params, float* packed_t, nf_stream_t stream);
+size_t nf_cbshape_packed_bwd_bf16_bytes(void);
+int nf_cbshape_pack_bwd_bf16(const float* const* params, void* packed_t_bf16, nf_stream_t stream);
+size_t nf_cbshape_packed_bwd_f16_bytes(void);
+int nf_cbshape_pack_bwd_f16(const float* const* params, void* stream_out, nf_stream_t stream);
+size_t nf_cbshape_grad_floats(void);
+size_t nf_cbshape_bwd_workspace_floats(int64_t n_points);
+int nf_cbshape_mlp_bwd(const float* packed, const float* packed_t, const float* cond, const float* saved, const float* d_raw,
+                  int64_t n_rays, int n_samples, float* workspace, size_t workspace_floats, float* grads, nf_stream_t stream);
+int nf_cbshape_mlp_bwd_bf16(const float* packed, const void* packed_t_bf16, const float* cond, const float* saved, const float* d_raw,
+                       int64_t n_rays, int n_samples, float* workspace, size_t workspace_floats, float* grads, nf_stream_t stream);
+int nf_cbshape_mlp_bwd_f16(const float* packed, const void* packed_t_f16, const float* cond, const float* saved, const float* d_raw,
+                      int64_t n_rays, int n_samples, float* workspace, size_t workspace_floats, float* grads, nf_stream_t stream);
+
+/* Measurement hook (tools/time_blendshape.py): nf_paper_mlp_bwd_stage_ms for the second family and the two classes on its kernels --
+ * one backward in arithmetic `precision` (0 exact f32 | 1 split-bf16 | 2 split-fp16; packed_t_any: the matching transposed image) with
+ * HIP events between its stages; synchronises the stream; stage_ms[3] (host) = {dX chain, weight-gradient GEMMs, reduce + scatter}.  */
+int nf_lcode_mlp_bwd_stage_ms(const float* packed, const void* packed_t_any, int precision, const float* cond, const float* saved,
+                              const float* d_raw, int64_t n_rays, int n_samples, float* workspace, size_t workspace_floats,
+                              float* grads, float* stage_ms, nf_stream_t stream);
+int nf_bshape_mlp_bwd_stage_ms(const float* packed, const void* packed_t_any, int precision, const float* cond, const float* saved,
+                               const float* d_raw, int64_t n_rays, int n_samples, float* workspace, size_t workspace_floats,
+                               float* grads, float* stage_ms, nf_stream_t stream);
+int nf_cbshape_mlp_bwd_stage_ms(const float* packed, const void* packed_t_any, int precision, const float* cond, const float* saved,
+                                const float* d_raw, int64_t n_rays, int n_samples, float* workspace, size_t workspace_floats,
+                                float* grads, float* stage_ms, nf_stream_t stream);
+
 /* ---- third model family: ConditionalBlendshapePaperSmallerNeRFModel (M:266-338) + run_network (T:9-33) -- the paper model without
  * layers_xyz.5 and layers_dir.3, with layers_dir.0 reading [feat 256 | PE4(dir) 24 | expr/3 76].  EXACT F32 ONLY (no split
  * arithmetics).  params: HOST array of 22 device pointers in state_dict order (layers_xyz.0..4, fc_feat, fc_alpha, layers_dir.0..2,
