@@ -10,7 +10,9 @@ radix select over exponential keys, torch's generator) instead of np.random.choi
 the reference's TensorBoard scalars / validation images (TR:415-424, 518-541; a JSON-lines file when the `tensorboard` package
 is absent), accumulated on the device and flushed on the iterations that print; on resume the latent codes and
 background are restored *into* the tensors the optimizer already owns (the reference re-wraps them and the optimizer
-keeps stepping the stale ones).
+keeps stepping the stale ones).  `--train-background [--supervised-background]` are the reference's
+`train_background` / `supervised_train_background` switches (TR:128-157, 376-381), which it sets in its source; without them the
+background is the fixed image of the dataset and its param group is inert, as in the reference's default.
 """
 from __future__ import annotations
 
@@ -49,7 +51,15 @@ def main(argv=None):
     ap.add_argument("--precision", choices=["f32", "f16x3", "bf16x3"], default=os.environ.get("NERFACE_MLP_PRECISION", "f32"),
                     help="arithmetic of the three training GEMM kernels: f32 (default) = the reference's; f16x3 = split-fp16, gradients "
                          "at least as accurate as the f32 kernels' at 2.4x the speed; bf16x3 = split-bf16, fastest (1e-4 per tensor)")
+    ap.add_argument("--train-background", action="store_true",
+                    help="learn the background (the reference's `train_background`, TR:128, 143-157, 188-193): it starts from the mean "
+                         "of the training images, requires grad and is stepped by the optimizer's second param group")
+    ap.add_argument("--supervised-background", action="store_true",
+                    help="add the reference's `supervised_train_background` term (TR:376-381): the squared distance of the background "
+                         "to the target pixel, weighted by the last fine weight, x 0.001; needs --train-background (TR:140)")
     args = ap.parse_args(argv)
+    if args.supervised_background and not args.train_background:
+        ap.error("--supervised-background requires --train-background")
     rank, world, dev = CM.init_distributed(args.backend)
     nerf.set_mlp_precision(args.precision)
     cfg = CM.load_config(args.config)
@@ -66,11 +76,19 @@ def main(argv=None):
     enc_xyz, enc_dir = CM.build_encoders(cfg)
     model_c, model_f = CM.build_models(cfg, dev)
     background = CM.load_background(cfg.dataset.basedir, H, W, dev)
+    if args.train_background:
+        # TR:143-157: the learned background starts from the mean training image and is a leaf that requires grad
+        with torch.no_grad():
+            idx = torch.as_tensor(np.asarray(i_train), dtype=torch.long)
+            background = torch.mean(images[idx][..., :3].to(torch.float32), dim=0).to(dev).contiguous()
+        background.requires_grad_(True)
     latent_codes = torch.zeros(len(i_train), 32, device=dev, requires_grad=True)
     trainable = list(model_c.parameters()) + (list(model_f.parameters()) if model_f is not None else []) + [latent_codes]
     groups = [{"params": trainable}]
     if background is not None:
-        groups.append({"params": background, "lr": cfg.optimizer.lr})          # inert 2nd group, kept for checkpoint compatibility
+        # 2nd group (TR:188-199): the learned background with --train-background, else inert and kept for checkpoint compatibility
+        groups.append({"params": background, "lr": cfg.optimizer.lr})
+    synced = trainable + ([background] if args.train_background else [])   # what the ranks broadcast and all-reduce
     # TR:193-199 `getattr(torch.optim, cfg.optimizer.type)`; nerf.optim holds one-launch forms of the same update rule (Adam) with
     # torch's state layout, so checkpoints stay interchangeable with the reference's
     optimizer = (getattr(nerf.optim, cfg.optimizer.type, None) or getattr(torch.optim, cfg.optimizer.type))(groups, lr=cfg.optimizer.lr)
@@ -84,13 +102,14 @@ def main(argv=None):
             with torch.no_grad():
                 latent_codes.copy_(ck["latent_codes"])
         if ck.get("background") is not None and background is not None:
-            background.copy_(ck["background"])
+            with torch.no_grad():
+                background.copy_(ck["background"])
         optimizer.load_state_dict(ck["optimizer_state_dict"])
         start_iter = int(ck["iter"])
-    D.broadcast_parameters(trainable)
+    D.broadcast_parameters(synced)
     # from here on every rank draws its OWN rays and noise: the shared seed above served the identical initialisation only
     torch.manual_seed(D.rank_seed(seed))
-    reducer = D.GradientAllReducer(trainable)
+    reducer = D.GradientAllReducer(synced)
     maps = [torch.from_numpy(m).to(device=dev, dtype=torch.float32) for m in importance_maps(bboxs[i_train].numpy(), H, W)]
     logdir = os.path.join(cfg.experiment.logdir, cfg.experiment.id)
     if rank == 0:
@@ -123,7 +142,7 @@ def main(argv=None):
         # rays, target pixels and background prior of the selected pixels only, one kernel (TR:302 builds the full 512 x 512
         # bundle every iteration and gathers four times, TR:325-330)
         ro, rd, target, bg = nerf.get_ray_batch(H, W, intrinsics, pose, sel, target_img, background)
-        rgb_c, _, _, rgb_f, _, _, _ = nerf.run_one_iter_of_nerf(
+        rgb_c, _, _, rgb_f, _, _, w_last = nerf.run_one_iter_of_nerf(
             H, W, intrinsics, model_c, model_f, ro, rd, cfg, mode="train", encode_position_fn=enc_xyz,
             encode_direction_fn=enc_dir, expressions=expr, background_prior=bg, latent_code=latent)
         # TR:355-387 (coarse + fine mse, 10 x 0.0005 x ||latent||) and -- in loss.backward() -- the gradients of those nodes: two launches
@@ -131,6 +150,11 @@ def main(argv=None):
         # and are read back (a host sync) only on the iterations that log or save
         loss, parts = nerf.training_loss(rgb_c[..., :3], rgb_f[..., :3] if rgb_f is not None else None, target[..., :3], latent)
         coarse_loss, fine_loss, code_loss, mse = parts[1], (parts[2] if rgb_f is not None else None), parts[3], parts[4]
+        bg_loss = None
+        if args.supervised_background:
+            # TR:376-381 on the 7th output: the background is pulled towards the target where the last sample's weight says it shows
+            bg_loss = torch.mean(((bg[..., :3] - target[..., :3]) ** 2).sum(1) * w_last) * 0.001
+            loss = loss + bg_loss
         loss.backward()
         reducer.reduce()
         optimizer.step()
@@ -151,6 +175,8 @@ def main(argv=None):
             if fine_loss is not None:
                 log.add_scalar("train/fine_loss", fine_loss, i)
             log.add_scalar("train/psnr", parts[5], i)
+            if bg_loss is not None:
+                log.add_scalar("train/bg_loss", bg_loss.detach(), i)
         if rank == 0 and logs_now:
             log.flush()
             print(f"[TRAIN] Iter: {i} Loss: {loss.item():.6f} PSNR: {nerf.mse2psnr(mse.item()):.4f} "
@@ -226,7 +252,7 @@ def main(argv=None):
         # replica consistency: after identical Adam steps on averaged gradients every rank must hold the same parameters, and
         # the ranks must have drawn different frames / rays (one checksum + the first draw per rank, gathered once at the end)
         import json
-        chk = torch.stack([p.detach().double().sum() for p in trainable]).sum().reshape(1)
+        chk = torch.stack([p.detach().double().sum() for p in synced]).sum().reshape(1)
         draw = torch.cat((torch.tensor([float(first_draw[0])], device=dev), first_draw[1].reshape(-1).float())).double()
         both = torch.cat((chk, draw))
         gathered = [torch.zeros_like(both) for _ in range(world)]

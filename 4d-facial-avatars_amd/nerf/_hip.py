@@ -122,6 +122,7 @@ _PROTOTYPES = {
     "nf_tiny_saved_floats": (_Z, [_L]),
     "nf_tiny_mlp_fwd_train": (C.c_int, [_P, _P, _P, _P, _I, _L, _I, _P, _P, _P]),
     "nf_render_volume_density_bwd": (C.c_int, [_P, _P, _P, _L, _I, _P, _P]),
+    "nf_render_volume_density_bwd_full": (C.c_int, [_P, _P, _P, _P, _P, _L, _I, _P, _P]),
     "nf_tiny_packed_bwd_floats": (_Z, []),
     "nf_tiny_pack_bwd": (C.c_int, [_P, _P, _P]),
     "nf_tiny_grad_floats": (_Z, []),
@@ -141,6 +142,7 @@ _PROTOTYPES = {
     "nf_selftest_dw_tables_flex": (C.c_int, [_I]),
     "nf_volume_render_fwd": (C.c_int, [_P, _P, _P, _P, _P, _L, _I, _I, _P, _P, _P, _P, _P]),
     "nf_volume_render_bwd": (C.c_int, [_P, _P, _P, _P, _P, _P, _L, _I, _I, _P, _P]),
+    "nf_volume_render_bwd_full": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _I, _P, _P, _P]),
     "nf_sample_pdf": (C.c_int, [_P, _P, _P, _L, _L, _I, _I, _P, _P]),
     "nf_sample_pdf_ex": (C.c_int, [_P, _P, _P, _L, _L, _I, _I, _P, _P, _P, _P]),
     "nf_resample_merge": (C.c_int, [_P, _P, _P, _L, _L, _I, _I, _P, _P, _P]),

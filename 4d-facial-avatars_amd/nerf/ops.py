@@ -130,6 +130,28 @@ def weighted_choice(weights: torch.Tensor, n: int, u: Optional[torch.Tensor] = N
     return idx
 
 
+class _SelectedBackground(torch.autograd.Function):
+    """bg (n, 3) = background (H, W, 3) at the selected pixels, as nf_ray_batch gathered it; the backward scatters the cotangent
+    back into a zero image (a pixel selected twice accumulates).  What makes a learned background (`train_background`, TR:143-157)
+    reachable through get_ray_batch; a pixel outside the image (ray_batch's out-of-range flag) receives nothing."""
+
+    @staticmethod
+    def forward(ctx, background, sel, bg):
+        ctx.save_for_backward(sel)
+        ctx.hw = tuple(background.shape[:2])
+        return bg.view_as(bg)
+
+    @staticmethod
+    def backward(ctx, g):
+        (sel,) = ctx.saved_tensors
+        h, w = ctx.hw
+        row, col = (torch.div(sel, w, rounding_mode="floor"), sel % w) if sel.dim() == 1 else (sel[:, 0], sel[:, 1])
+        ok = (row >= 0) & (row < h) & (col >= 0) & (col < w) if sel.dim() == 2 else (sel >= 0) & (sel < h * w)
+        d = torch.zeros((h, w, 3), dtype=g.dtype, device=g.device)
+        d.index_put_((row.clamp(0, h - 1), col.clamp(0, w - 1)), g * ok[:, None].to(g.dtype), accumulate=True)
+        return d, None, None
+
+
 def ray_batch(height: int, width: int, fx: float, fy: float, cx: float, cy: float, c2w: torch.Tensor, sel: torch.Tensor,
               image: Optional[torch.Tensor] = None, background: Optional[torch.Tensor] = None, check: bool = False):
     """Rays of the selected pixels only (sel (n, 2) int64 {row, col}, or (n,) flat pixel indices row * W + col) -- bit-identical to
@@ -163,6 +185,8 @@ def ray_batch(height: int, width: int, fx: float, fy: float, cx: float, cy: floa
                                      H.ptr(target), H.ptr(bg), H.ptr(flag), H.stream_ptr(dev)), "nf_ray_batch")
     if check and int(flag.item()):
         raise IndexError("ray_batch: a selected pixel lies outside the image")
+    if background is not None and background.requires_grad and torch.is_grad_enabled():
+        bg = _SelectedBackground.apply(background, sel, bg)
     return ro, rd, target, bg
 
 
@@ -630,6 +654,47 @@ def volume_render_bwd(raw, z, rd, noise, bg, d_rgb, white_background=False):
     return d_raw
 
 
+def _cotangent(name: str, t, shape, what: str):
+    """A cotangent of the full integrator backward: None (zero), or float32 of exactly `shape`; anything else is refused by name,
+    before anything is allocated or launched."""
+    if t is None:
+        return None
+    if not torch.is_tensor(t) or tuple(t.shape) != tuple(shape):
+        got = tuple(t.shape) if torch.is_tensor(t) else type(t).__name__
+        raise ValueError(f"{what}: {name} must have shape {tuple(shape)}, got {got}")
+    if t.dtype != torch.float32:
+        raise ValueError(f"{what}: {name} must be float32, got {t.dtype}")
+    return t if t.is_contiguous() else t.contiguous()
+
+
+def volume_render_bwd_full(raw, z, rd, noise, bg, d_rgb=None, d_disp=None, d_acc=None, d_weights=None, d_w_last=None,
+                           white_background=False, need_d_bg=False):
+    """The integrator's backward through every output: cotangents of rgb (R, 3), disp (R), acc (R), weights (R, S) and of
+    weights[:, -1] alone (R), each optional -> (d_raw (R, S, 4), d_bg (R, 3) or None).  d_bg, the gradient of the background prior
+    (the last sample's colour), is computed when need_d_bg.  volume_render_bwd stays the path of a backward that carries d_rgb only."""
+    what = "volume_render_bwd_full"
+    n_rays, n_samples = z.shape
+    d_rgb = _cotangent("d_rgb", d_rgb, (n_rays, 3), what)
+    d_disp = _cotangent("d_disp", d_disp, (n_rays,), what)
+    d_acc = _cotangent("d_acc", d_acc, (n_rays,), what)
+    d_weights = _cotangent("d_weights", d_weights, (n_rays, n_samples), what)
+    d_w_last = _cotangent("d_w_last", d_w_last, (n_rays,), what)
+    if d_rgb is None and d_disp is None and d_acc is None and d_weights is None and d_w_last is None:
+        raise ValueError(f"{what}: no cotangent given (d_rgb, d_disp, d_acc, d_weights and d_w_last are all None)")
+    if need_d_bg and bg is None:
+        raise ValueError(f"{what}: need_d_bg without a background prior (bg is None)")
+    check_bwd_samples(n_samples, what)
+    dev = H.require_device(raw, z, rd, noise, bg, d_rgb, d_disp, d_acc, d_weights, d_w_last)
+    d_raw = torch.empty((n_rays, n_samples, 4), dtype=torch.float32, device=dev)
+    d_bg = torch.empty((n_rays, 3), dtype=torch.float32, device=dev) if need_d_bg else None
+    with torch.cuda.device(dev):
+        H.check(H.lib().nf_volume_render_bwd_full(H.ptr(raw), H.ptr(z), H.ptr(rd), H.ptr(noise), H.ptr(bg), H.ptr(d_rgb), H.ptr(d_disp),
+                                                  H.ptr(d_acc), H.ptr(d_weights), H.ptr(d_w_last), n_rays, n_samples,
+                                                  1 if white_background else 0, H.ptr(d_raw), H.ptr(d_bg), H.stream_ptr(dev)),
+                "nf_volume_render_bwd_full")
+    return d_raw, d_bg
+
+
 def render_volume_density(raw, depth):
     """tiny_nerf's compositing (TN:68-107: no background sample, no +1e-6, spacing not scaled by |rd|): raw (n_rays, S, 4),
     depth (n_rays, S) -> (rgb_map (n_rays, 3), depth_map (n_rays), acc_map (n_rays))."""
@@ -654,6 +719,26 @@ def render_volume_density_bwd(raw, depth, d_rgb):
     with torch.cuda.device(dev):
         H.check(H.lib().nf_render_volume_density_bwd(H.ptr(raw), H.ptr(depth), H.ptr(d_rgb), n_rays, n_samples, H.ptr(d_raw),
                                                      H.stream_ptr(dev)), "nf_render_volume_density_bwd")
+    return d_raw
+
+
+def render_volume_density_bwd_full(raw, depth, d_rgb=None, d_depth=None, d_acc=None):
+    """Backward of render_volume_density through all three outputs: cotangents of rgb_map (R, 3), depth_map (R) and acc_map (R),
+    each optional -> d_raw (R, S, 4)."""
+    what = "render_volume_density_bwd_full"
+    n_rays, n_samples = depth.shape
+    d_rgb = _cotangent("d_rgb", d_rgb, (n_rays, 3), what)
+    d_depth = _cotangent("d_depth", d_depth, (n_rays,), what)
+    d_acc = _cotangent("d_acc", d_acc, (n_rays,), what)
+    if d_rgb is None and d_depth is None and d_acc is None:
+        raise ValueError(f"{what}: no cotangent given (d_rgb, d_depth and d_acc are all None)")
+    check_bwd_samples(n_samples, what)
+    dev = H.require_device(raw, depth, d_rgb, d_depth, d_acc)
+    d_raw = torch.empty((n_rays, n_samples, 4), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        H.check(H.lib().nf_render_volume_density_bwd_full(H.ptr(raw), H.ptr(depth), H.ptr(d_rgb), H.ptr(d_depth), H.ptr(d_acc), n_rays,
+                                                          n_samples, H.ptr(d_raw), H.stream_ptr(dev)),
+                "nf_render_volume_density_bwd_full")
     return d_raw
 
 

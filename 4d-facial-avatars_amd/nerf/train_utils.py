@@ -49,10 +49,24 @@ def run_network(network_fn, pts, ray_batch, chunksize, embed_fn, embeddirs_fn, e
 # --------------------------------------------------------------------------------------------------
 # autograd boundary: one Function per ray chunk
 # --------------------------------------------------------------------------------------------------
+def _integrator_backward(raw, z, rd, noise, bg, d_rgb, d_disp, d_acc, d_w_last, white, need_d_bg):
+    """d_raw (and d_bg) of one pass, or (None, None) when no cotangent reached it.  A pass whose only cotangent is d_rgb, with a
+    background that needs no gradient, is the rgb-only kernel: the trainer's step launches what it always did."""
+    if d_rgb is None and d_disp is None and d_acc is None and d_w_last is None:
+        return None, None
+    if d_disp is None and d_acc is None and d_w_last is None and not need_d_bg:
+        return ops.volume_render_bwd(raw, z, rd, noise, bg, d_rgb, white), None
+    return ops.volume_render_bwd_full(raw, z, rd, noise, bg, ops._c(d_rgb), ops._c(d_disp), ops._c(d_acc), None, ops._c(d_w_last),
+                                      white, need_d_bg)
+
+
 class _RenderChunk(torch.autograd.Function):
-    """Coarse+fine render of one ray chunk.  Inputs that can receive gradients: the 2x26 model parameters
-    and the latent code (nothing upstream of the MLP is learnable).  Outputs: the 7-tuple of
-    T:162; only rgb_coarse / rgb_fine are differentiable (the trainer's loss uses nothing else)."""
+    """Coarse+fine render of one ray chunk.  Inputs that can receive gradients: the background prior, the 2x26 model parameters
+    and the latent code (nothing upstream of the MLP is learnable; the background is the trainer's
+    `train_background` leaf, TR:143-157).  Outputs: the 7-tuple of T:162, all differentiable; the coarse weights that feed the
+    resampler stay detached (T:124).  `need_grad` is one switch for the chunk: when the background prior is the ONLY input that
+    requires grad (frozen networks and latent code), both MLP forwards still save their training state and backward still runs
+    hip_backward for gradients that autograd then drops -- correct, wasted work, and not a case the trainer produces."""
 
     @staticmethod
     def forward(ctx, cfg, ro, rd, rd_view, bg, expr, latent, t_rand, noise_c, u, noise_f, n_params_c, *params):
@@ -60,7 +74,7 @@ class _RenderChunk(torch.autograd.Function):
         near, far, nc, nf = cfg["near"], cfg["far"], cfg["num_coarse"], cfg["num_fine"]
         white = cfg["white_background"]
         need_grad = cfg["need_grad"]
-        ctx.set_materialize_grads(False)       # the five non-differentiable outputs would each cost a zero-fill kernel per backward
+        ctx.set_materialize_grads(False)       # an output the loss does not read would cost a zero-fill kernel per backward
         dev = ro.device
         n_rays = ro.shape[0]
 
@@ -86,8 +100,6 @@ class _RenderChunk(torch.autograd.Function):
             ctx.state_c = state_c
             if ctx.has_fine:
                 ctx.fine = (z_f, raw_f, state_f)
-        nondiff = [o for i, o in enumerate(outs) if not (i == 0 or (ctx.has_fine and i == 3))]
-        ctx.mark_non_differentiable(*nondiff)
         return tuple(outs)
 
     @staticmethod
@@ -96,26 +108,29 @@ class _RenderChunk(torch.autograd.Function):
         rd, bg, noise_c, noise_f, z_c, raw_c, latent = ctx.saved_tensors
         model_c, model_f = cfg["model_coarse"], cfg["model_fine"]
         white = cfg["white_background"]
-        d_rgb_c = grads[0]
-        g_latent = None
+        need_d_bg = bg is not None and ctx.needs_input_grad[4]
+        g_latent = g_bg = None
         grads_c = [None] * ctx.n_params_c
         grads_f = []
-        if d_rgb_c is not None:
-            d_raw_c = ops.volume_render_bwd(raw_c, z_c, rd, noise_c, bg, d_rgb_c, white)
+        # outputs: rgb_c, disp_c, acc_c, [rgb_f, disp_f, acc_f,] w_last -- the last weight is the coarse pass's when there is no fine one
+        d_raw_c, g_bg = _integrator_backward(raw_c, z_c, rd, noise_c, bg, grads[0], grads[1], grads[2],
+                                             None if ctx.has_fine else grads[3], white, need_d_bg)
+        if d_raw_c is not None:
             grads_c, g_latent = model_c.hip_backward(ctx.state_c, z_c, d_raw_c)
         ctx.state_c = None
         if ctx.has_fine:
             z_f, raw_f, state_f = ctx.fine
-            d_rgb_f = grads[3]
             grads_f = [None] * len(model_f.hip_param_list())
-            if d_rgb_f is not None:
-                d_raw_f = ops.volume_render_bwd(raw_f, z_f, rd, noise_f, bg, d_rgb_f, white)
+            d_raw_f, g_bg_f = _integrator_backward(raw_f, z_f, rd, noise_f, bg, grads[3], grads[4], grads[5], grads[6], white, need_d_bg)
+            if d_raw_f is not None:
                 grads_f, gl = model_f.hip_backward(state_f, z_f, d_raw_f)
                 g_latent = gl if g_latent is None else g_latent + gl
+            if g_bg_f is not None:
+                g_bg = g_bg_f if g_bg is None else g_bg + g_bg_f
             ctx.fine = None
         g_latent = g_latent.reshape(latent.shape) if (ctx.needs_input_grad[6] and g_latent is not None) else None
         # inputs: cfg, ro, rd, rd_view, bg, expr, latent, t_rand, noise_c, u, noise_f, n_params_c, *params
-        return (None, None, None, None, None, None, g_latent, None, None, None, None, None, *grads_c, *grads_f)
+        return (None, None, None, None, g_bg, None, g_latent, None, None, None, None, None, *grads_c, *grads_f)
 
 
 def _check_encoders(encode_position_fn, encode_direction_fn):
@@ -168,7 +183,8 @@ def _render_rays(ro, rd, rd_view, model_coarse, model_fine, options, mode, expre
     noise_std = float(m.radiance_field_noise_std)
     params_c = model_coarse.hip_param_list()
     params_f = model_fine.hip_param_list() if has_fine else []
-    need_grad = torch.is_grad_enabled() and (latent_code.requires_grad or any(p.requires_grad for p in params_c + params_f))
+    need_grad = torch.is_grad_enabled() and (latent_code.requires_grad or any(p.requires_grad for p in params_c + params_f)
+                                             or (background_prior is not None and background_prior.requires_grad))
     # sample counts no render kernel is built for are refused here: before a random number is drawn or a kernel launched (the forward
     # integrator takes any count, so without this a training step beyond the backward's limit would only fail inside backward())
     ops.check_sample_counts(nc, nf if has_fine else 0, need_grad)

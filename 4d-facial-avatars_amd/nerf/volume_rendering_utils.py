@@ -7,23 +7,29 @@ from . import ops
 
 
 class _VolumeRender(torch.autograd.Function):
-    """K5 forward/backward.  Differentiable w.r.t. `radiance_field` through rgb_map only (that is the only
-    path the trainer's loss uses, train_transformed_rays.py:355-387); the other outputs are marked
-    non-differentiable."""
+    """K5 forward/backward.  Differentiable w.r.t. `radiance_field` and `background_prior` through all four outputs (rgb_map,
+    disp_map, acc_map, weights).  A backward that carries only d_rgb and needs no background gradient -- the trainer's loss,
+    train_transformed_rays.py:355-375 -- is the rgb-only kernel (ops.volume_render_bwd); anything else the full one."""
 
     @staticmethod
     def forward(ctx, raw, z, rd, noise, bg, white_background):
         rgb, disp, acc, w = ops.volume_render_fwd(raw, z, rd, noise, bg, white_background)
         ctx.save_for_backward(raw, z, rd, noise, bg)
         ctx.white_background = white_background
-        ctx.mark_non_differentiable(disp, acc, w)
+        ctx.set_materialize_grads(False)       # an output the loss does not read arrives as None, not as a zero-filled tensor
         return rgb, disp, acc, w
 
     @staticmethod
     def backward(ctx, d_rgb, d_disp, d_acc, d_w):
         raw, z, rd, noise, bg = ctx.saved_tensors
-        d_raw = ops.volume_render_bwd(raw, z, rd, noise, bg, d_rgb.contiguous(), ctx.white_background)
-        return d_raw, None, None, None, None, None
+        need_d_bg = bg is not None and ctx.needs_input_grad[4]
+        if d_rgb is None and d_disp is None and d_acc is None and d_w is None:
+            return None, None, None, None, None, None
+        if d_disp is None and d_acc is None and d_w is None and not need_d_bg:
+            return ops.volume_render_bwd(raw, z, rd, noise, bg, d_rgb.contiguous(), ctx.white_background), None, None, None, None, None
+        d_raw, d_bg = ops.volume_render_bwd_full(raw, z, rd, noise, bg, ops._c(d_rgb), ops._c(d_disp), ops._c(d_acc), ops._c(d_w), None,
+                                                 ctx.white_background, need_d_bg)
+        return d_raw, None, None, None, d_bg, None
 
 
 def volume_render_radiance_field(radiance_field, depth_values, ray_directions, radiance_field_noise_std=0.0,

@@ -202,6 +202,14 @@ int nf_volume_render_fwd(const float* raw, const float* z, const float* rd, cons
 int nf_volume_render_bwd(const float* raw, const float* z, const float* rd, const float* noise,
                          const float* bg, const float* d_rgb, int64_t n_rays, int n_samples,
                          int white_background, float* d_raw, nf_stream_t stream);
+/* The full backward: a cotangent of every output, each optional (NULL = zero; all NULL is NF_EINVAL): d_rgb (R,3), d_disp (R),
+ * d_acc (R), d_weights (R,S), and d_w_last (R), a cotangent of weights[:, -1] alone (so that no (R,S) tensor is needed for it).
+ * d_bg (R,3) or NULL: the gradient of the background prior (= weights[:, -1] * d_rgb; needs bg).  Same limits as
+ * nf_volume_render_bwd, which stays the path of a backward that carries d_rgb only.                    */
+int nf_volume_render_bwd_full(const float* raw, const float* z, const float* rd, const float* noise,
+                              const float* bg, const float* d_rgb, const float* d_disp, const float* d_acc,
+                              const float* d_weights, const float* d_w_last, int64_t n_rays, int n_samples,
+                              int white_background, float* d_raw, float* d_bg, nf_stream_t stream);
 
 /* ---- second model family: ConditionalBlendshapeLearnableCodeNeRFModel.forward (M:590-636) + run_network (T:9-33), inference.
  * params: HOST array of 16 device pointers in state_dict order (layer1, layers_xyz.0..2, layers_dir.0, fc_alpha, fc_rgb,
@@ -428,6 +436,9 @@ int nf_tiny_mlp_fwd_train(const float* packed, const float* ro, const float* rd,
                           int64_t n_rays, int n_samples, float* raw, float* saved, nf_stream_t stream);
 int nf_render_volume_density_bwd(const float* raw, const float* depth, const float* d_rgb, int64_t n_rays, int n_samples,
                                  float* d_raw, nf_stream_t stream);
+/* the same through all three outputs (rgb_map, depth_map, acc_map); each cotangent optional, all NULL is NF_EINVAL */
+int nf_render_volume_density_bwd_full(const float* raw, const float* depth, const float* d_rgb, const float* d_depth,
+                                      const float* d_acc, int64_t n_rays, int n_samples, float* d_raw, nf_stream_t stream);
 size_t nf_tiny_packed_bwd_floats(void);
 int nf_tiny_pack_bwd(const float* const* params, float* packed_t, nf_stream_t stream);
 size_t nf_tiny_grad_floats(void);
