@@ -4,7 +4,7 @@
 // Weighted sampling without replacement = the n smallest of the keys e_i / w_i with e_i ~ Exp(1) (Efraimidis & Spirakis 2006:
 // successive draws proportional to the remaining weights, which is what np.random.choice(replace=False, p=...) does).  The
 // caller supplies uniform numbers u_i in [0, 1) (torch.rand on the device: the draw stays under torch's generator and seeds);
-// e_i = -log(1 - u_i).  The n smallest keys are found by an exact three-level radix select on the 32 key bits (12 + 12 + 8;
+// e_i = -log(1 - u_i); the sign bit of the key is cleared, so that u_i = 0 gives the key +0 and the item is always taken.  The n smallest keys are found by an exact three-level radix select on the 32 key bits (12 + 12 + 8;
 // positive floats order like their bit patterns): each level is one launch that histograms the digit of the keys that match the
 // prefix found so far (LDS histogram per workgroup, merged with global atomics), and the LAST workgroup to finish scans the
 // 4096 bins, extends the prefix and clears the histogram for the next level.  Then an ORDERED compaction in two launches: every
@@ -34,9 +34,11 @@ struct NfChoiceState {            // workspace header (uint32 words): zeroed by 
 __device__ __forceinline__ unsigned nf_choice_key(const float* __restrict__ w, const float* __restrict__ u, int64_t i) {
     const float wi = w[i];
     if (!(wi > 0.0f)) return 0x7f800000u;                         // never chosen (+inf); NaN weights too
-    const float e = -logf(1.0f - u[i]);                            // u in [0, 1) -> e in [0, 16.7]
+    const float e = -logf(1.0f - u[i]);                            // u in [0, 1) -> e in [0, 16.7]; u = 0 gives -0.0f
     const float k = e / wi;
-    const unsigned b = __float_as_uint(k);
+    // no key is negative, so clearing the sign bit changes one value only: -0.0 (0x80000000, from u = 0), which the clamp below would
+    // take for an overflow, becomes the key 0 that it is.  (On the bits: the compiler folds 0.0f - x into a negation.)
+    const unsigned b = __float_as_uint(k) & 0x7fffffffu;
     return b > 0x7f7fffffu ? 0x7f7fffffu : b;                      // finite: an overflowing quotient still beats weight 0
 }
 

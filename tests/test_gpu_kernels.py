@@ -423,6 +423,7 @@ def test_weighted_choice_is_the_n_smallest_exponential_keys(hip_lib, gpu):
     checked against a float64 evaluation of the keys (boundary items may swap within fp32 rounding of the key) --, distinct,
     in range, never an item of weight 0; ties in the key, n = 1, n = all positive items, too few positive items."""
     from nerf import ops
+    from tests import util as U
     g = torch.Generator().manual_seed(101)
     for n_items, n in ((262144, 2048), (5000, 4948), (5000, 4900), (1000, 1), (777, 300)):     # 4948 = every item of positive weight
         w = torch.full((n_items,), 0.1)
@@ -435,11 +436,10 @@ def test_weighted_choice_is_the_n_smallest_exponential_keys(hip_lib, gpu):
         assert bool((idx[1:] > idx[:-1]).all()) or n == 1                     # ascending (deterministic batch order)
         assert int(idx.min()) >= 0 and int(idx.max()) < n_items and len(set(idx.tolist())) == n
         assert bool((w[idx] > 0).all())
-        key = -torch.log1p(-u.double()) / w.double()
-        key[w == 0] = float("inf")
+        key = U.choice_reference_keys(w, u)                                   # the kernel's logf(1.0f - u): 1 - u rounded to float32
         chosen = torch.zeros(n_items, dtype=torch.bool)
         chosen[idx] = True
-        assert float(key[chosen].max()) <= float(key[~chosen].min()) * (1 + 1e-5)
+        assert float(key[chosen].max()) <= float(key[~chosen].min()) * (1 + U.CHOICE_KEY_D)
     # ties: identical weights and identical random numbers -> any n of them
     idx = ops.weighted_choice(torch.ones(4096, device=gpu), 100, torch.full((4096,), 0.25, device=gpu), check=True).cpu()
     assert len(set(idx.tolist())) == 100

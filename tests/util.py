@@ -122,3 +122,22 @@ def parse_bench_stdout(text):
     assert len(lines[1]) < 6144 and "bench_detail" not in compact
     return compact, detail["bench_detail"]
 
+
+
+# Relative error bound of one device key of the ray draw (csrc/nf_choice.hip: k = (0 - logf(1 - u)) / w), used on either side of
+# the n-th smallest float64 key.  ROCm's HIP math API reference gives the accuracy of logf; that document is not part of a ROCm
+# installation, so the bound is taken as FOUR float32 ulps (an ulp is at most 2^-23 of the value), not from the kernel: it has
+# to cover logf plus a correctly rounded division (half an ulp) on each of the two keys that a comparison involves.
+# Worst relative gap seen on an MI355X (largest chosen float64 key / smallest unchosen one - 1, against the float64 keys of
+# choice_reference_keys): -1.3e-3 and -5.5e-3 in the two cases of tests/test_gpu_small_kernels.py::test_choice_wide_range_band, i.e.
+# never positive -- the draw was exactly the n smallest float64 keys, and the band was not needed.
+CHOICE_KEY_D = 4 * 2.0 ** -23
+
+
+def choice_reference_keys(w, u):
+    """float64 keys of the ray draw with the kernel's definition of the argument: 1 - u is ROUNDED to float32 (the kernel computes
+    logf(1.0f - u), which differs from log1p(-u) for small u); items that can never be chosen (weight not > 0, NaN) get +inf."""
+    one_minus_u = torch.tensor(1.0, dtype=torch.float32) - u.float()
+    key = (0.0 - torch.log(one_minus_u.double())) / w.double()
+    key[~(w > 0)] = float("inf")
+    return key
