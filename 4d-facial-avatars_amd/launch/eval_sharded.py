@@ -111,6 +111,9 @@ def _main(argv=None):
                          "self-PSNR -- north_star's 1e-4 dB gate measured on YOUR sequence against its own test images.  Default: 50 for "
                          "bf16x3 / f16x2 (nerf.gate.VERIFY_BY_DEFAULT), 0 (off) for f16x3; 0 switches it off")
     ap.add_argument("--gate-strict", action="store_true", help="with --verify-gate: raise if a verified frame misses the 1e-4 dB gate")
+    ap.add_argument("--metrics", action="store_true",
+                    help="also compute L1, PSNR and SSIM of every frame as written (its uint8 bytes) against its test image, on the device, "
+                         "and write savedir/metrics.txt in the layout of the reference's nerf/metrics.py (without LPIPS)")
     ap.add_argument("--backend", choices=["nccl", "gloo"], default=os.environ.get("NERFACE_DIST_BACKEND", "nccl"))
     ap.add_argument("--as-shipped", action="store_true",
                     help="render exactly what eval_transformed_rays.py renders as shipped (EV:420-446): ablate = 'view_dir' -- pose and "
@@ -125,6 +128,9 @@ def _main(argv=None):
     if args.verify_gate and args.as_shipped:
         print("WARNING: --verify-gate is ignored with --as-shipped (the shipped ablation render has no per-frame test image to measure against)")
         args.verify_gate = 0
+    if args.metrics and args.as_shipped:
+        print("WARNING: --metrics is ignored with --as-shipped (the shipped ablation render has no per-frame test image to measure against)")
+        args.metrics = False
     cfg = CM.load_config(args.config)
     images, poses, render_poses, hwf, i_split, expressions, _, bboxs = nerf.load_flame_data(
         cfg.dataset.basedir, half_res=cfg.dataset.half_res, testskip=cfg.dataset.testskip, test=True)
@@ -180,6 +186,9 @@ def _main(argv=None):
     # waits for the GPU (PNG output and post-processing are asynchronous), so host clocks would time the launches, not the render
     marks = []
     gate_rows = []                                                        # (frame, |dPSNR| vs the f32 frame, self-PSNR): device scalars, read at the end
+    # --metrics: one result table and one workspace for this rank's frames, allocated here; per frame the loop adds one launch
+    table = ops.ImageMetricsTable(len(mine), H, W, dev) if args.metrics else None
+    metric_marks = []                                                     # --metrics: the launch's own event pair per frame
     t_start = time.time()
     for i in mine:
         ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -232,6 +241,15 @@ def _main(argv=None):
         want_n = (args.save_normals or shipped is not None) and out[4] is not None            # EV:469-471 always writes normals/
         rgb_u8, normals_u8 = ops.eval_postprocess(rgb[..., :3], out[4] if want_n else None, out[6], intrinsics, want_normals=want_n)
         writer.submit(rgb_u8, os.path.join(args.savedir, f"{i:04d}.png"))
+        if args.metrics:
+            # the frame's bytes as they go into the PNG against the test image's own bytes (uploaded as the loader holds it and
+            # quantised on the device: one frame's worth of memory, and the stream is idle here anyway -- the loop is paced by the
+            # host once per frame).  Inside the frame's event pair, and timed on its own as well (metrics_s)
+            ev_m0, ev_m1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            ev_m0.record()
+            table.add(rgb_u8, nerf.quantize_image(images[i].to(dev)[..., :3].reshape(H, W, 3)).contiguous())
+            ev_m1.record()
+            metric_marks.append((ev_m0, ev_m1))
         if normals_u8 is not None:
             writer.submit(normals_u8, os.path.join(args.savedir, "normals", f"{i:04d}.png"))
         if args.save_disparity_image:
@@ -252,7 +270,7 @@ def _main(argv=None):
     # what the loop cost (rank-local): GPU seconds per frame from the HIP events, wall of the loop including the PNG tail
     main.last_stats = {"frames": len(times), "gpu_s_per_frame": sum(times) / len(times) if times else None,
                        "gpu_s_total": sum(times), "wall_s": t_end - t_start, "wall_s_until_gpu_idle": t_gpu_done - t_start,
-                       "frames_s": len(times) / (t_end - t_start) if times else None}
+                       "frames_s": len(times) / (t_end - t_start) if times else None, "frame_s": times}
     if gate_rows:
         rows = [(f, float(d), float(sp)) for f, d, sp in gate_rows]
         worst = max(rows, key=lambda r: r[1])
@@ -266,6 +284,20 @@ def _main(argv=None):
             if args.gate_strict:
                 raise RuntimeError(msg)
             print("WARNING: " + msg)
+    if args.metrics:
+        from nerf import metrics as MET
+        local = table.values[:table.count].cpu().tolist()                                              # the one read-back: l1, mse, psnr, ssim
+        rows = D.gather_rows([(f, v[0], v[2], v[3]) for f, v in zip(mine, local)])                     # every rank's frames, in frame order
+        m_s = [a.elapsed_time(b) * 1e-3 for a, b in metric_marks]
+        main.last_stats["metrics_s"], main.last_stats["metrics_frame_s"] = (sum(m_s) / len(m_s) if m_s else None), m_s
+        if rank == 0:
+            main.last_stats["metrics"] = MET.write_metrics_file(os.path.join(args.savedir, "metrics.txt"),
+                                                                [(f"{f:04d}.png", l1, psnr, ssim) for f, l1, psnr, ssim in rows],
+                                                                os.path.join(cfg.dataset.basedir, "test"), args.savedir)
+            print(MET.summary_text(main.last_stats["metrics"], os.path.join(cfg.dataset.basedir, "test"), args.savedir))
+        if m_s:
+            print(f"[rank {rank}] --metrics: {1e6 * sum(m_s) / len(m_s):.0f} us per frame (test image upload + one launch; included in the "
+                  f"frame time below)")
     if times:
         print(f"[rank {rank}] rendered {len(times)} of {n} frames, avg time per image: {sum(times) / len(times):.3f} s "
               f"(GPU time per frame; wall {t_end - t_start:.1f} s including PNG output)")

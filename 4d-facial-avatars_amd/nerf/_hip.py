@@ -154,6 +154,8 @@ _PROTOTYPES = {
     "nf_train_loss_fwd": (C.c_int, [_P, _P, _P, _L, _P, _I, _F, _F, _P, _P]),
     "nf_train_loss_bwd": (C.c_int, [_P, _P, _P, _L, _P, _I, _F, _F, _P, _P, _P, _P, _P, _P]),
     "nf_sort_rows": (C.c_int, [_P, _L, _I, _P, _P]),
+    "nf_image_metrics_workspace_bytes": (_Z, [_L, _I, _I]),
+    "nf_image_metrics": (C.c_int, [_P, _P, _L, _I, _I, C.c_double, _P, _Z, _P, _P, _P]),
 }
 _FAMILY_ENTRY_POINTS = {          # <prefix>_<name> of a family with every arithmetic (the names nerf/ops.py calls), one signature per name
     "packed_floats": (_Z, []), "cond_floats": (_Z, []), "pack": (C.c_int, [_P, _P, _P]),

@@ -49,6 +49,17 @@ def gather_frame_order(n_frames: int, world: int) -> List[tuple]:
     return [(i % world, i // world) for i in range(n_frames)]
 
 
+def gather_rows(rows: Sequence[tuple], group=None) -> List[tuple]:
+    """Host rows (tuples that start with the global frame index) of every rank, on every rank, sorted by frame: what the eval
+    launcher needs to write one per-sequence table from frames that were rendered rank r, r + W, ...  The identity at world size 1."""
+    _, world = world_info()
+    if _skip_collectives(world):
+        return sorted(rows)
+    parts = [None] * dist.get_world_size(group)
+    dist.all_gather_object(parts, list(rows), group=group)
+    return sorted(r for part in parts for r in part)
+
+
 class GradientAllReducer:
     """Flat-buffer gradient averaging for [model_coarse, model_fine, latent table]: per step ONE multi-tensor copy into a
     persistent flat buffer, ONE all-reduce, one scale, one multi-tensor copy back -- no per-parameter kernels and no

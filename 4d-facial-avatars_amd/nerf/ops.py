@@ -869,3 +869,85 @@ def eval_postprocess(rgb, depthmap=None, weights=None, intrinsics=None, want_nor
         H.check(H.lib().nf_eval_postprocess(H.ptr(rgb), H.ptr(depthmap), H.ptr(weights), h, w, fx, fy, cx, cy, H.ptr(rgb_u8),
                                             H.ptr(normals), H.stream_ptr(dev)), "nf_eval_postprocess")
     return rgb_u8, normals
+
+
+# ---------------------------------------------------------------------------------------- image metrics
+def quantize_image(x: torch.Tensor) -> torch.Tensor:
+    """Float image in [0, 1] -> uint8 by clamp and ROUND TO NEAREST: recovers k from float32(k / 255) for all 256 bytes (a test
+    image as the loaders hold it).  The rendered frame is quantised by truncation instead (eval_postprocess, EV:184-190): those
+    are the bytes written to disk."""
+    return (x.clamp(0.0, 1.0) * 255.0).round().to(torch.uint8)
+
+
+METRIC_NAMES = ("l1", "mse", "psnr", "ssim")
+
+
+def image_metrics(pred_u8: torch.Tensor, target_u8: torch.Tensor, ssim_data_range: float = 2.0) -> dict:
+    """L1, MSE, PSNR and SSIM of uint8 images (H, W, 3) or (N, H, W, 3) against their targets, one launch for the batch and no host
+    synchronisation: {"l1", "mse", "psnr", "ssim"} float64 and {"abs_sum", "sq_sum"} int64 device tensors, shape (N,) (0-d for a
+    single image).  The values are the reference's nerf/metrics.py on the float images byte / 255: np.mean(np.abs(.)), compare_psnr
+    (data range 1) and compare_ssim(multichannel=True), whose data range for float input is 2 (the dtype's range (-1, 1)): pass
+    ssim_data_range=1.0 for the textbook constants."""
+    for name, t in (("pred_u8", pred_u8), ("target_u8", target_u8)):
+        if not torch.is_tensor(t) or t.dtype != torch.uint8:
+            raise TypeError(f"image_metrics: {name} must be a uint8 tensor, got {getattr(t, 'dtype', type(t))} "
+                            "(nerf.quantize_image turns a float image in [0, 1] into one)")
+    if pred_u8.shape != target_u8.shape:
+        raise ValueError(f"image_metrics: shapes differ: {tuple(pred_u8.shape)} and {tuple(target_u8.shape)}")
+    if pred_u8.dim() not in (3, 4) or pred_u8.shape[-1] != 3:
+        raise ValueError(f"image_metrics: expected (H, W, 3) or (N, H, W, 3), got {tuple(pred_u8.shape)}")
+    h, w = int(pred_u8.shape[-3]), int(pred_u8.shape[-2])
+    if h < 7 or w < 7:
+        raise ValueError(f"image_metrics: the 7 x 7 SSIM window needs H >= 7 and W >= 7, got {h} x {w}")
+    if not (pred_u8.is_cuda and target_u8.is_cuda):
+        raise RuntimeError("nerf (MI355X build): tensors must live on a ROCm device (`device='cuda'`); "
+                           "there is no CPU path in this package")
+    if pred_u8.device != target_u8.device:
+        raise RuntimeError("nerf (MI355X build): tensors are on different devices")
+    single = pred_u8.dim() == 3
+    a, b, dev = pred_u8.contiguous(), target_u8.contiguous(), pred_u8.device
+    n = 1 if single else int(a.shape[0])
+    out_f = torch.empty((n, 4), dtype=torch.float64, device=dev)
+    out_i = torch.empty((n, 2), dtype=torch.int64, device=dev)
+    if n:
+        lib = H.lib()
+        ws_bytes = int(lib.nf_image_metrics_workspace_bytes(n, h, w))
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            H.check(lib.nf_image_metrics(H.ptr(a), H.ptr(b), n, h, w, float(ssim_data_range), H.ptr(ws), ws_bytes, H.ptr(out_f),
+                                         H.ptr(out_i), H.stream_ptr(dev)), "nf_image_metrics")
+    pick = (lambda t, k: t[0, k]) if single else (lambda t, k: t[:, k])
+    res = {name: pick(out_f, k) for k, name in enumerate(METRIC_NAMES)}
+    res["abs_sum"], res["sq_sum"] = pick(out_i, 0), pick(out_i, 1)
+    return res
+
+
+class ImageMetricsTable:
+    """The metrics of a sequence, one frame per call, into buffers allocated once: an (n_frames, 4) float64 table (METRIC_NAMES), an
+    (n_frames, 2) int64 table (sum |d|, sum d^2) and one workspace.  add() is nothing but the launch -- no allocation, no new tensor,
+    no host synchronisation -- which is what a render loop that the host paces wants (launch/eval_sharded.py --metrics)."""
+
+    def __init__(self, n_frames: int, height: int, width: int, device, ssim_data_range: float = 2.0):
+        if height < 7 or width < 7:
+            raise ValueError(f"ImageMetricsTable: the 7 x 7 SSIM window needs H >= 7 and W >= 7, got {height} x {width}")
+        self.shape, self.device, self.data_range, self.count = (int(height), int(width), 3), torch.device(device), float(ssim_data_range), 0
+        self.values = torch.zeros((n_frames, 4), dtype=torch.float64, device=self.device)
+        self.sums = torch.zeros((n_frames, 2), dtype=torch.int64, device=self.device)
+        self._lib = H.lib()
+        self._ws_bytes = int(self._lib.nf_image_metrics_workspace_bytes(1, height, width))
+        self._ws = torch.empty(self._ws_bytes, dtype=torch.uint8, device=self.device)
+
+    def add(self, pred_u8: torch.Tensor, target_u8: torch.Tensor) -> int:
+        """Launch the metrics of one (H, W, 3) uint8 pair into the next row; returns the row."""
+        for t in (pred_u8, target_u8):
+            if t.dtype != torch.uint8 or tuple(t.shape) != self.shape or t.device != self.device or not t.is_contiguous():
+                raise ValueError(f"ImageMetricsTable.add: expected contiguous uint8 {self.shape} on {self.device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+        row = self.count
+        if row >= self.values.shape[0]:
+            raise IndexError("ImageMetricsTable.add: the table is full")
+        h, w, _ = self.shape
+        H.check(self._lib.nf_image_metrics(H.ptr(pred_u8), H.ptr(target_u8), 1, h, w, self.data_range, H.ptr(self._ws), self._ws_bytes,
+                                           self.values.data_ptr() + 32 * row, self.sums.data_ptr() + 16 * row, H.stream_ptr(self.device)),
+                "nf_image_metrics")
+        self.count = row + 1
+        return row

@@ -476,6 +476,19 @@ int nf_flex_mlp_bwd(int num_layers, const float* packed_t, const float* saved, c
 int nf_eval_postprocess(const float* rgb, const float* depthmap, const float* weights, int height, int width, float fx,
                         float fy, float cx_w, float cy_h, uint8_t* rgb_u8, uint8_t* normals_u8, nf_stream_t stream);
 
+/* ---- image metrics of rendered frames -- replaces what nerf/metrics.py (two_folders) takes from skimage: L1, compare_psnr and
+ *      compare_ssim(im1, im2, multichannel=True) of float images byte / 255, for n image pairs in one launch -------------------
+ * a, b: uint8 [n][H][W][3], contiguous (a = rendered frame, b = test image).  out_f64 [n][4] = {L1 = mean |a - b| / 255,
+ * MSE = mean ((a - b) / 255)^2, PSNR = 10 log10(1 / MSE) (+inf for identical images), SSIM}; out_i64 [n][2] = {sum |a - b|,
+ * sum (a - b)^2} in byte units.  SSIM: 7 x 7 uniform window, sample covariance, C1 = (0.01 R)^2, C2 = (0.03 R)^2 with
+ * R = ssim_range, mean over the windows inside the image and the channels; window statistics are exact integers, S is evaluated in
+ * float64.  R = 2.0 reproduces the reference (that skimage takes the float dtype's range (-1, 1)); 1.0 is the textbook value.
+ * Results are bit-identical from run to run (fixed-order reduction through `workspace`, no floating-point atomics).
+ * NF_EINVAL: NULL pointers, H < 7, W < 7, n < 0, workspace_bytes below nf_image_metrics_workspace_bytes(n, H, W); n == 0: no launch. */
+size_t nf_image_metrics_workspace_bytes(int64_t n, int height, int width);
+int nf_image_metrics(const uint8_t* a, const uint8_t* b, int64_t n, int height, int width, double ssim_range, void* workspace,
+                     size_t workspace_bytes, double* out_f64, int64_t* out_i64, nf_stream_t stream);
+
 /* ---- K6: inverse-CDF sampler -- replaces sample_pdf_2 (H:344-387) --------------------------------- */
 /* bins (R,n_bins), weights (R,n_bins-1); u: row r at u + r*u_row_stride, n_out values
  * (u_row_stride = n_out for torch.rand draws, 0 to broadcast the det-mode linspace(0,1,n_out) table). */
