@@ -57,6 +57,10 @@ def main(argv=None):
     ap.add_argument("--supervised-background", action="store_true",
                     help="add the reference's `supervised_train_background` term (TR:376-381): the squared distance of the background "
                          "to the target pixel, weighted by the last fine weight, x 0.001; needs --train-background (TR:140)")
+    ap.add_argument("--graph", action="store_true",
+                    help="capture the iteration body once in a HIP graph and replay it (nerf.GraphedTrainer: ray choice to Adam step "
+                         "without the host in the loop); single rank only -- validation, logging and checkpoints are unchanged and "
+                         "checkpoints load into runs with and without it")
     args = ap.parse_args(argv)
     if args.supervised_background and not args.train_background:
         ap.error("--supervised-background requires --train-background")
@@ -91,7 +95,12 @@ def main(argv=None):
     synced = trainable + ([background] if args.train_background else [])   # what the ranks broadcast and all-reduce
     # TR:193-199 `getattr(torch.optim, cfg.optimizer.type)`; nerf.optim holds one-launch forms of the same update rule (Adam) with
     # torch's state layout, so checkpoints stay interchangeable with the reference's
-    optimizer = (getattr(nerf.optim, cfg.optimizer.type, None) or getattr(torch.optim, cfg.optimizer.type))(groups, lr=cfg.optimizer.lr)
+    if args.graph:
+        if cfg.optimizer.type != "Adam":
+            raise NotImplementedError(f"--graph steps nerf.optim.Adam(capturable=True); the config asks for {cfg.optimizer.type}")
+        optimizer = nerf.optim.Adam(groups, lr=cfg.optimizer.lr, capturable=True)
+    else:
+        optimizer = (getattr(nerf.optim, cfg.optimizer.type, None) or getattr(torch.optim, cfg.optimizer.type))(groups, lr=cfg.optimizer.lr)
     start_iter = 0
     if args.load_checkpoint and os.path.exists(args.load_checkpoint):
         ck = torch.load(args.load_checkpoint, map_location=dev)
@@ -129,42 +138,60 @@ def main(argv=None):
         # every checkpoint (the only iterations that synchronise with the host anyway)
         nerf.ops.set_f16_train_probe_every(cfg.experiment.print_every)
     n_rays = cfg.nerf.train.num_random_rays
+    trainer = None
+    if args.graph:
+        # the schedule of the loop below (lr_new), evaluated by the Adam kernel from its own step count
+        optimizer.set_lr_schedule(cfg.optimizer.lr, cfg.scheduler.lr_decay_factor, cfg.scheduler.lr_decay * 1000)
+        trainer = nerf.GraphedTrainer(model_c, model_f, latent_codes, background, optimizer, H, W, intrinsics, cfg, args.precision,
+                                      supervised_background=args.supervised_background)       # raises when world > 1
+        rows = torch.arange(len(i_train), device=dev)
     t0 = time.time()
     first_draw = None
     for i in range(start_iter, cfg.experiment.train_iters):
         k = int(np.random.randint(len(i_train)))              # one frame per rank per step (TR:289)
         img_idx = int(i_train[k])
         target_img, pose, expr = stager.fetch(img_idx)
-        latent = latent_codes[k]
-        sel = nerf.choose_rays(maps[k], n_rays)               # TR:320-322 on the device: n distinct pixels, p = the importance map
-        if first_draw is None:
-            first_draw = (img_idx, sel[:16].clone())
-        # rays, target pixels and background prior of the selected pixels only, one kernel (TR:302 builds the full 512 x 512
-        # bundle every iteration and gathers four times, TR:325-330)
-        ro, rd, target, bg = nerf.get_ray_batch(H, W, intrinsics, pose, sel, target_img, background)
-        rgb_c, _, _, rgb_f, _, _, w_last = nerf.run_one_iter_of_nerf(
-            H, W, intrinsics, model_c, model_f, ro, rd, cfg, mode="train", encode_position_fn=enc_xyz,
-            encode_direction_fn=enc_dir, expressions=expr, background_prior=bg, latent_code=latent)
-        # TR:355-387 (coarse + fine mse, 10 x 0.0005 x ||latent||) and -- in loss.backward() -- the gradients of those nodes: two launches
-        # (nerf.training_loss) instead of ~20; parts = [loss, coarse, fine, code loss, coarse + fine, its PSNR, ||latent||] stay on the device
-        # and are read back (a host sync) only on the iterations that log or save
-        loss, parts = nerf.training_loss(rgb_c[..., :3], rgb_f[..., :3] if rgb_f is not None else None, target[..., :3], latent)
-        coarse_loss, fine_loss, code_loss, mse = parts[1], (parts[2] if rgb_f is not None else None), parts[3], parts[4]
-        bg_loss = None
-        if args.supervised_background:
-            # TR:376-381 on the 7th output: the background is pulled towards the target where the last sample's weight says it shows
-            bg_loss = torch.mean(((bg[..., :3] - target[..., :3]) ** 2).sum(1) * w_last) * 0.001
-            loss = loss + bg_loss
-        loss.backward()
-        reducer.reduce()
-        optimizer.step()
-        optimizer.zero_grad()
-        lr_new = cfg.optimizer.lr * (cfg.scheduler.lr_decay_factor ** (i / (cfg.scheduler.lr_decay * 1000)))
-        for g in optimizer.param_groups:
-            g["lr"] = lr_new
+        if trainer is not None:
+            # the whole body below as one graph replay; its scalars are a static device buffer, copied once so that the log may keep them
+            trainer.step(pose, expr, target_img, maps[k], rows[k])
+            if first_draw is None:
+                first_draw = (img_idx, trainer.selected[:16].clone())
+            parts = trainer.parts.clone()
+            loss, coarse_loss, fine_loss, code_loss, mse = parts[0], parts[1], (parts[2] if trainer.has_fine else None), parts[3], parts[4]
+            bg_loss = parts[7] if args.supervised_background else None
+        else:
+            latent = latent_codes[k]
+            sel = nerf.choose_rays(maps[k], n_rays)               # TR:320-322 on the device: n distinct pixels, p = the importance map
+            if first_draw is None:
+                first_draw = (img_idx, sel[:16].clone())
+            # rays, target pixels and background prior of the selected pixels only, one kernel (TR:302 builds the full 512 x 512
+            # bundle every iteration and gathers four times, TR:325-330)
+            ro, rd, target, bg = nerf.get_ray_batch(H, W, intrinsics, pose, sel, target_img, background)
+            rgb_c, _, _, rgb_f, _, _, w_last = nerf.run_one_iter_of_nerf(
+                H, W, intrinsics, model_c, model_f, ro, rd, cfg, mode="train", encode_position_fn=enc_xyz,
+                encode_direction_fn=enc_dir, expressions=expr, background_prior=bg, latent_code=latent)
+            # TR:355-387 (coarse + fine mse, 10 x 0.0005 x ||latent||) and -- in loss.backward() -- the gradients of those nodes: two launches
+            # (nerf.training_loss) instead of ~20; parts = [loss, coarse, fine, code loss, coarse + fine, its PSNR, ||latent||] stay on the device
+            # and are read back (a host sync) only on the iterations that log or save
+            loss, parts = nerf.training_loss(rgb_c[..., :3], rgb_f[..., :3] if rgb_f is not None else None, target[..., :3], latent)
+            coarse_loss, fine_loss, code_loss, mse = parts[1], (parts[2] if rgb_f is not None else None), parts[3], parts[4]
+            bg_loss = None
+            if args.supervised_background:
+                # TR:376-381 on the 7th output: the background is pulled towards the target where the last sample's weight says it shows
+                bg_loss = torch.mean(((bg[..., :3] - target[..., :3]) ** 2).sum(1) * w_last) * 0.001
+                loss = loss + bg_loss
+            loss.backward()
+            reducer.reduce()
+            optimizer.step()
+            optimizer.zero_grad()
+            lr_new = cfg.optimizer.lr * (cfg.scheduler.lr_decay_factor ** (i / (cfg.scheduler.lr_decay * 1000)))
+            for g in optimizer.param_groups:
+                g["lr"] = lr_new
         logs_now = i % cfg.experiment.print_every == 0 or i == cfg.experiment.train_iters - 1
         saves_now = i % cfg.experiment.save_every == 0 or i == cfg.experiment.train_iters - 1
-        if f16 and (logs_now or saves_now):
+        if trainer is not None and (logs_now or saves_now):
+            trainer.check_range()
+        elif f16 and (logs_now or saves_now):
             # every rank raises TOGETHER (flag MAX-reduced) if any rank's step since the last poll overflowed fp16 -- before the
             # checkpoint below is written
             nerf.ops.check_f16_range(model_c, model_f, sync_ranks=True)

@@ -153,6 +153,9 @@ _PROTOTYPES = {
     "nf_adam_step": (C.c_int, [_P, _P, _P, _P, _P, _I, _F, _F, _F, _F, _L, _P]),
     "nf_train_loss_fwd": (C.c_int, [_P, _P, _P, _L, _P, _I, _F, _F, _P, _P]),
     "nf_train_loss_bwd": (C.c_int, [_P, _P, _P, _L, _P, _I, _F, _F, _P, _P, _P, _P, _P, _P]),
+    "nf_adam_step_dev": (C.c_int, [_P, _P, _P, _P, _P, _I, _F, _F, _F, _P, _P]),
+    "nf_train_loss_bg_fwd": (C.c_int, [_P, _P, _P, _L, _P, _I, _F, _F, _P, _P, _F, _P, _P]),
+    "nf_train_loss_bg_bwd": (C.c_int, [_P, _P, _P, _L, _P, _I, _F, _F, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P, _P]),
     "nf_sort_rows": (C.c_int, [_P, _L, _I, _P, _P]),
     "nf_image_metrics_workspace_bytes": (_Z, [_L, _I, _I]),
     "nf_image_metrics": (C.c_int, [_P, _P, _L, _I, _I, C.c_double, _P, _Z, _P, _P, _P]),

@@ -555,6 +555,8 @@ def f16_guard(model, ro, rd, z, rd_view, expr, latent, near, far, training: bool
     range.  Inference probes once per (weights, conditioning), i.e. once per frame and model; in training the weights move every
     step, so a model's first call and every f16_train_probe_every()-th after it are probed."""
     state = model.__dict__
+    if training and torch.cuda.is_current_stream_capturing():
+        return                           # a probe reads the device: nerf.GraphedTrainer probes before it captures and polls the flag outside
     if training:
         n_calls = state["_f16_train_calls"] = state.get("_f16_train_calls", 0) + 1
         if not (_f16_train_probe_every[0] == 1 or n_calls % _f16_train_probe_every[0] == 1):
@@ -776,20 +778,67 @@ class _TrainingLoss(torch.autograd.Function):
         return d_c, d_f, None, d_l, None, None
 
 
-def training_loss(rgb_coarse, rgb_fine, target, latent=None, code_weight: float = 0.0005, code_scale: float = 10.0):
+class _TrainingLossBg(torch.autograd.Function):
+    """_TrainingLoss plus the background-supervision term of TR:376-381 (nf_train_loss_bg_fwd / nf_train_loss_bg_bwd): the same two
+    launches, and the gradients of the selected background pixels and of the last sample's weight besides."""
+
+    @staticmethod
+    def forward(ctx, rgb_c, rgb_f, target, latent, bg, w_last, code_weight, code_scale, bg_weight):
+        dev = H.require_device(rgb_c, rgb_f, target, latent, bg, w_last)
+        out = torch.empty((8,), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            H.check(H.lib().nf_train_loss_bg_fwd(H.ptr(rgb_c), H.ptr(rgb_f), H.ptr(target), rgb_c.numel(), H.ptr(latent),
+                                                 0 if latent is None else latent.numel(), float(code_weight), float(code_scale), H.ptr(bg),
+                                                 H.ptr(w_last), float(bg_weight), H.ptr(out), H.stream_ptr(dev)), "nf_train_loss_bg_fwd")
+        ctx.save_for_backward(rgb_c, rgb_f, target, latent, bg, w_last, out)
+        ctx.consts = (float(code_weight), float(code_scale), float(bg_weight))
+        parts = out.detach()
+        ctx.mark_non_differentiable(parts)
+        return out[0], parts
+
+    @staticmethod
+    def backward(ctx, go, _go_parts):
+        rgb_c, rgb_f, target, latent, bg, w_last, out = ctx.saved_tensors
+        dev = rgb_c.device
+        go = go.to(torch.float32).contiguous()
+        d_c = torch.empty_like(rgb_c)
+        d_f = torch.empty_like(rgb_f) if rgb_f is not None else None
+        d_l = torch.empty_like(latent) if latent is not None else None
+        d_bg, d_w = torch.empty_like(bg), torch.empty_like(w_last)
+        with torch.cuda.device(dev):
+            H.check(H.lib().nf_train_loss_bg_bwd(H.ptr(rgb_c), H.ptr(rgb_f), H.ptr(target), rgb_c.numel(), H.ptr(latent),
+                                                 0 if latent is None else latent.numel(), ctx.consts[0], ctx.consts[1], H.ptr(bg),
+                                                 H.ptr(w_last), ctx.consts[2], H.ptr(out), H.ptr(go), H.ptr(d_c), H.ptr(d_f), H.ptr(d_l),
+                                                 H.ptr(d_bg), H.ptr(d_w), H.stream_ptr(dev)), "nf_train_loss_bg_bwd")
+        return d_c, d_f, None, d_l, d_bg, d_w, None, None, None
+
+
+def training_loss(rgb_coarse, rgb_fine, target, latent=None, code_weight: float = 0.0005, code_scale: float = 10.0,
+                  background=None, last_weight=None, background_weight: float = 0.001):
     """The trainer's loss (TR:355-387) fused: returns (loss, parts) with parts = [loss, coarse mse, fine mse, code loss, coarse + fine,
     psnr of coarse + fine, ||latent||] (detached, for logging); `loss` is differentiable w.r.t. rgb_coarse, rgb_fine and latent.
-    rgb_fine / latent may be None.  Colour maps and target: the same shape, float32 (made contiguous if they are not)."""
-    for t in (rgb_coarse, rgb_fine, target, latent):                     # before _c(): a float64 map must not be down-cast silently
+    rgb_fine / latent may be None.  Colour maps and target: the same shape, float32 (made contiguous if they are not).
+    background (n_rays, 3) + last_weight (n_rays): add the background-supervision term of TR:376-381, mean(sum((background -
+    target)^2, 1) * last_weight) * background_weight, in the same two launches; `loss` is then differentiable w.r.t. both as well
+    and `parts` ends with the term (8 entries).  With both None the entry points and launches are the ones above."""
+    for t in (rgb_coarse, rgb_fine, target, latent, background, last_weight):   # before _c(): a float64 map must not be down-cast silently
         if t is not None and t.dtype != torch.float32:
             raise TypeError("training_loss: float32 tensors only")
+    if (background is None) != (last_weight is None):
+        raise ValueError("training_loss: the background term needs both `background` (n_rays, 3) and `last_weight` (n_rays)")
     rgb_c, tgt = _c(rgb_coarse), _c(target)
     rgb_f = _c(rgb_fine) if rgb_fine is not None else None
     lat = _c(latent) if latent is not None else None
     if tgt.shape != rgb_c.shape or (rgb_f is not None and rgb_f.shape != rgb_c.shape):
         raise ValueError(f"training_loss: colour maps {tuple(rgb_c.shape)} / {None if rgb_f is None else tuple(rgb_f.shape)} and target "
                          f"{tuple(tgt.shape)} must have one shape")
-    return _TrainingLoss.apply(rgb_c, rgb_f, tgt, lat, code_weight, code_scale)
+    if background is None:
+        return _TrainingLoss.apply(rgb_c, rgb_f, tgt, lat, code_weight, code_scale)
+    bg, w_last = _c(background), _c(last_weight)
+    if rgb_c.dim() != 2 or rgb_c.shape[1] != 3 or bg.shape != rgb_c.shape or tuple(w_last.shape) != (rgb_c.shape[0],):
+        raise ValueError(f"training_loss: the background term needs (n_rays, 3) colour maps and background and an (n_rays,) last_weight; "
+                         f"got {tuple(rgb_c.shape)}, {tuple(bg.shape)}, {tuple(w_last.shape)}")
+    return _TrainingLossBg.apply(rgb_c, rgb_f, tgt, lat, bg, w_last, code_weight, code_scale, background_weight)
 
 
 # ---------------------------------------------------------------------------------------- K6 / K7

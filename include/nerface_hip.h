@@ -558,6 +558,27 @@ int nf_train_loss_bwd(const float* rgb_coarse, const float* rgb_fine, const floa
                       int n_latent, float code_weight, float code_scale, const float* out7, const float* grad_out,
                       float* d_rgb_coarse, float* d_rgb_fine, float* d_latent, nf_stream_t stream);
 
+/* ---- the same two pieces in the form a captured HIP graph can replay (additive to ABI 5) ---------------------------------------
+ * nf_adam_step_dev: nf_adam_step with the step count and the learning-rate schedule in a device block the caller owns, instead of
+ *      host scalars (kernel arguments are frozen in a captured graph).  state: 32 bytes, 8-byte aligned:
+ *        { float step (completed steps); int32 ticket (0 between launches); double lr0, decay_factor, decay_steps }.
+ *      Step i = `step` before the launch runs with lr = i == 0 ? lr0 : lr0 * decay_factor ^ ((i - 1) / decay_steps) (the lr the
+ *      trainer set at the end of step i - 1, TR:395-400; double, rounded to f32 once) and bias corrections of t = i + 1 in
+ *      nf_adam_step's operation order; the launch leaves step = i + 1 (one thread stores it after every workgroup has read i).
+ * nf_train_loss_bg_*: nf_train_loss_* plus the trainer's background-supervision term (TR:376-381)
+ *        bg_loss = mean_r(sum_c (bg[r, c] - target[r, c])^2 * w_last[r]) * bg_weight
+ *      n_elems = 3 n_rays (colour maps, target, bg: (n_rays, 3) contiguous f32; w_last: (n_rays)).  out8 = out7 with the term added
+ *      to out8[0], and out8[7] = bg_loss.  Backward: also d_bg (n_rays, 3) and d_w_last (n_rays).                                */
+int nf_adam_step_dev(float* const* params, const float* const* grads, float* const* exp_avg, float* const* exp_avg_sq,
+                     const int64_t* numel, int n_tensors, float beta1, float beta2, float eps, void* state, nf_stream_t stream);
+int nf_train_loss_bg_fwd(const float* rgb_coarse, const float* rgb_fine, const float* target, int64_t n_elems, const float* latent,
+                         int n_latent, float code_weight, float code_scale, const float* bg, const float* w_last, float bg_weight,
+                         float* out8, nf_stream_t stream);
+int nf_train_loss_bg_bwd(const float* rgb_coarse, const float* rgb_fine, const float* target, int64_t n_elems, const float* latent,
+                         int n_latent, float code_weight, float code_scale, const float* bg, const float* w_last, float bg_weight,
+                         const float* out8, const float* grad_out, float* d_rgb_coarse, float* d_rgb_fine, float* d_latent,
+                         float* d_bg, float* d_w_last, nf_stream_t stream);
+
 /* ---- K7: per-ray ascending sort -- replaces torch.sort(...)[0] at T:126 --------------------------- */
 int nf_sort_rows(const float* in, int64_t n_rows, int n_cols, float* out, nf_stream_t stream);
 

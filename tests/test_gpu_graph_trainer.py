@@ -1,0 +1,369 @@
+"""GPU: the captured training step -- nf_adam_step_dev, nf_train_loss_bg_*, nerf.GraphedTrainer against the eager loop body of
+launch/train_sharded.py, and the launcher's --graph switch."""
+import ctypes as C
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+import yaml
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for _p in (os.path.join(ROOT, "tools"), os.path.join(ROOT, "4d-facial-avatars_amd")):
+    if _p not in sys.path:
+        sys.path.insert(0, _p)
+
+SIZE, N_RAYS, N_FRAMES = 32, 64, 3
+INTRINSICS = np.array([-1.5 * SIZE, 1.5 * SIZE, 0.5, 0.5])
+LR0, DECAY_FACTOR, DECAY_STEPS = 5.0e-4, 0.1, 10.0            # a schedule that moves the rate visibly within a handful of steps
+
+
+# ------------------------------------------------------------------------------------------------------- nf_adam_step_dev
+def _device_lr(step_done):
+    s = np.float64(np.float32(step_done))
+    return float(np.float32(LR0 if s == 0.0 else np.float64(LR0) * np.power(np.float64(DECAY_FACTOR), (s - 1.0) / np.float64(DECAY_STEPS))))
+
+
+def test_adam_step_dev_equals_the_host_scalar_kernel_bit_for_bit(hip_lib, gpu):
+    """5 tensors (1, 63, 64, 257, 70001 elements: below / at / over a 4-wide lane group, over a 1024-element workgroup, many
+    workgroups), 4 consecutive steps with a decaying rate: parameters and both moments equal nf_adam_step fed the same lr and step."""
+    from nerf import _hip as H
+    g = torch.Generator().manual_seed(3)
+    sizes = (1, 63, 64, 257, 70001)
+    mk = lambda: [torch.randn(n, generator=g).to(gpu) for n in sizes]
+    p_ref, grads = mk(), [mk() for _ in range(4)]
+    p_dev = [p.clone() for p in p_ref]
+    m_ref, v_ref = [torch.zeros_like(p) for p in p_ref], [torch.zeros_like(p) for p in p_ref]
+    m_dev, v_dev = [torch.zeros_like(p) for p in p_ref], [torch.zeros_like(p) for p in p_ref]
+    state = torch.zeros(8, dtype=torch.float32, device=gpu)
+    state[2:8].view(torch.float64).copy_(torch.tensor([LR0, DECAY_FACTOR, DECAY_STEPS], dtype=torch.float64))
+    n = len(sizes)
+    arr = lambda ts: (C.c_void_p * n)(*[int(t.data_ptr()) for t in ts])
+    numel = (C.c_int64 * n)(*sizes)
+    s = H.stream_ptr(gpu)
+    lrs = []
+    for k in range(4):
+        lr = _device_lr(k)
+        lrs.append(lr)
+        H.check(hip_lib.nf_adam_step(arr(p_ref), arr(grads[k]), arr(m_ref), arr(v_ref), numel, n, lr, 0.9, 0.999, 1e-8, k + 1, s), "nf_adam_step")
+        H.check(hip_lib.nf_adam_step_dev(arr(p_dev), arr(grads[k]), arr(m_dev), arr(v_dev), numel, n, 0.9, 0.999, 1e-8,
+                                         int(state.data_ptr()), s), "nf_adam_step_dev")
+        assert float(state[0]) == k + 1.0
+    assert lrs[0] == float(np.float32(LR0)) and lrs[1] == lrs[0] and lrs[3] < lrs[2] < lrs[1]        # step i runs on the rate set after step i - 1
+    for a, b in zip(p_ref + m_ref + v_ref, p_dev + m_dev + v_dev):
+        assert torch.equal(a, b)
+    assert float(state[0]) == 4.0 and int(state.view(torch.int32)[1]) == 0
+    assert hip_lib.nf_adam_step_dev(arr(p_dev), arr(grads[0]), arr(m_dev), arr(v_dev), numel, n, 0.9, 0.999, 1e-8, 0, s) != 0   # no state block
+
+
+def test_adam_step_dev_table_split_over_several_launches(hip_lib, gpu):
+    """70 tensors: more than the 64 of one launch's table, so the entry point launches twice.  The first launch reads the step
+    count and leaves it alone, the last one with work increments it -- once per step; a trailing table chunk of empty tensors does
+    not take that role.  3 steps, equal to nf_adam_step bit for bit."""
+    from nerf import _hip as H
+    g = torch.Generator().manual_seed(4)
+    for sizes in ([1 + (7 * i) % 37 for i in range(70)], [5] * 64 + [0] * 6 + [3] * 2 + [0] * 60):
+        n = len(sizes)
+        mk = lambda: [torch.randn(max(k, 1), generator=g).to(gpu)[:k] for k in sizes]
+        p_ref, grads = mk(), [mk() for _ in range(3)]
+        p_dev = [p.clone() for p in p_ref]
+        m_ref, v_ref = [torch.zeros_like(p) for p in p_ref], [torch.zeros_like(p) for p in p_ref]
+        m_dev, v_dev = [torch.zeros_like(p) for p in p_ref], [torch.zeros_like(p) for p in p_ref]
+        state = torch.zeros(8, dtype=torch.float32, device=gpu)
+        state[2:8].view(torch.float64).copy_(torch.tensor([LR0, DECAY_FACTOR, DECAY_STEPS], dtype=torch.float64))
+        # an empty tensor has a NULL data pointer, which both entry points refuse: hand them a valid address and numel 0
+        arr = lambda ts: (C.c_void_p * n)(*[int(t.data_ptr()) or int(state.data_ptr()) for t in ts])
+        numel = (C.c_int64 * n)(*sizes)
+        s = H.stream_ptr(gpu)
+        for k in range(3):
+            H.check(hip_lib.nf_adam_step(arr(p_ref), arr(grads[k]), arr(m_ref), arr(v_ref), numel, n, _device_lr(k), 0.9, 0.999, 1e-8,
+                                         k + 1, s), "nf_adam_step")
+            H.check(hip_lib.nf_adam_step_dev(arr(p_dev), arr(grads[k]), arr(m_dev), arr(v_dev), numel, n, 0.9, 0.999, 1e-8,
+                                             int(state.data_ptr()), s), "nf_adam_step_dev")
+            assert float(state[0]) == k + 1.0 and int(state.view(torch.int32)[1]) == 0
+        for a, b in zip(p_ref + m_ref + v_ref, p_dev + m_dev + v_dev):
+            assert torch.equal(a, b)
+
+
+# ------------------------------------------------------------------------------------------------------- nf_train_loss_bg_*
+def _loss_formula(rgb_c, rgb_f, target, latent, bg, w_last):
+    """TR:355-387 + TR:376-381 restated in torch, in the dtype of its arguments."""
+    mse = lambda a: torch.mean((a - target) ** 2)
+    loss = mse(rgb_c) + (mse(rgb_f) if rgb_f is not None else 0.0) + 10.0 * (0.0005 * torch.norm(latent))
+    return loss + torch.mean(((bg - target) ** 2).sum(1) * w_last) * 0.001
+
+
+def _loss_case(n, fine, dtype, device):
+    g = torch.Generator().manual_seed(100 + n + int(fine))
+    mk = lambda *s: torch.rand(*s, generator=g, dtype=torch.float64).to(device=device, dtype=dtype)
+    return [mk(n, 3), mk(n, 3) if fine else None, mk(n, 3), mk(32) - 0.5, mk(n, 3), mk(n)]
+
+
+def _loss_and_grads(fn, args):
+    leaves = [None if a is None else a.clone().requires_grad_(i != 2) for i, a in enumerate(args)]
+    loss = fn(*leaves)
+    loss = loss[0] if isinstance(loss, tuple) else loss
+    loss.backward()
+    return [loss.detach().reshape(1)] + [leaves[i].grad for i in (0, 1, 3, 4, 5) if leaves[i] is not None]
+
+
+def _rel_err(got, ref):
+    return max(float((g.double() - r).abs().max() / r.abs().max()) for g, r in zip(got, ref))
+
+
+# error of torch's own float32 evaluation of _loss_formula against float64 (max over the 8 cases of the per-tensor max |x - ref| / max |ref|,
+# loss and the five gradients), measured on an MI355X; the fused kernels are held to twice that
+EAGER_F32_ERR = 1.9e-7
+LOSS_BG_TOL = 2.0 * EAGER_F32_ERR
+
+
+@pytest.mark.parametrize("fine", [True, False])
+@pytest.mark.parametrize("n", [1, 31, 64, 2048])
+def test_train_loss_bg_matches_float64_autograd(hip_lib, gpu, n, fine):
+    """nf_train_loss_bg_fwd / _bwd (through nerf.training_loss) against float64 torch autograd on the restated formula: loss and the
+    gradients w.r.t. rgb_coarse, rgb_fine, latent, bg and w_last.
+    Tolerance: torch-eager float32 on the same formula and inputs is off by up to 1.89e-7 on an MI355X (relative to each tensor's
+    largest reference entry; 1.1e-7 .. 1.9e-7 over these 8 cases), so the kernels are allowed twice that, 3.8e-7; they measure
+    1.1e-7 .. 1.8e-7.  Both figures are printed."""
+    import nerf
+    ref = _loss_and_grads(_loss_formula, _loss_case(n, fine, torch.float64, gpu))
+    eager = _loss_and_grads(_loss_formula, _loss_case(n, fine, torch.float32, gpu))
+    fused = _loss_and_grads(lambda c, f, t, l, b, w: nerf.training_loss(c, f, t, l, background=b, last_weight=w),
+                            _loss_case(n, fine, torch.float32, gpu))
+    e_eager, e_fused = _rel_err(eager, ref), _rel_err(fused, ref)
+    print(f"n={n} fine={fine}: torch-eager f32 error {e_eager:.3e}, fused kernels {e_fused:.3e}, allowed {LOSS_BG_TOL:.3e}")
+    assert e_fused <= LOSS_BG_TOL
+    # parts: the seven scalars of the plain loss, then the term
+    args = _loss_case(n, fine, torch.float32, gpu)
+    loss_bg, parts_bg = nerf.training_loss(args[0], args[1], args[2], args[3], background=args[4], last_weight=args[5])
+    loss, parts = nerf.training_loss(args[0], args[1], args[2], args[3])
+    assert parts.numel() == 7 and parts_bg.numel() == 8 and torch.equal(parts_bg[1:7], parts[1:7])
+    want = float(torch.mean(((args[4].double() - args[2].double()) ** 2).sum(1) * args[5].double()) * 0.001)
+    assert abs(float(parts_bg[7]) - want) <= LOSS_BG_TOL * abs(want)
+
+
+@pytest.mark.parametrize("fine", [True, False])
+def test_training_loss_without_the_term_is_todays(hip_lib, gpu, fine):
+    """background=None, last_weight=None: the existing entry points, outputs bit-identical to calling them directly."""
+    import nerf
+    from nerf import _hip as H
+    c, f, t, l, _, _ = _loss_case(257, fine, torch.float32, gpu)
+    leaves = [x.clone().requires_grad_(True) if x is not None else None for x in (c, f, l)]
+    loss, parts = nerf.training_loss(leaves[0], leaves[1], t, leaves[2], background=None, last_weight=None)
+    loss.backward()
+    out = torch.empty(7, device=gpu)
+    s = H.stream_ptr(gpu)
+    H.check(hip_lib.nf_train_loss_fwd(H.ptr(c), H.ptr(f), H.ptr(t), c.numel(), H.ptr(l), 32, 0.0005, 10.0, H.ptr(out), s), "fwd")
+    d_c, d_f, d_l = torch.empty_like(c), (torch.empty_like(f) if fine else None), torch.empty_like(l)
+    H.check(hip_lib.nf_train_loss_bwd(H.ptr(c), H.ptr(f), H.ptr(t), c.numel(), H.ptr(l), 32, 0.0005, 10.0, H.ptr(out),
+                                      H.ptr(torch.ones((), device=gpu)), H.ptr(d_c), H.ptr(d_f), H.ptr(d_l), s), "bwd")
+    assert torch.equal(parts, out) and torch.equal(loss.detach(), out[0])
+    assert torch.equal(leaves[0].grad, d_c) and torch.equal(leaves[2].grad, d_l) and (not fine or torch.equal(leaves[1].grad, d_f))
+
+
+# ------------------------------------------------------------------------------------------------------- graph against eager
+class _Run:
+    """Models, latent table, background, capturable optimizer and 3 frames, built the same way from a seed."""
+
+    def __init__(self, gpu, model_type, train_background=False, constant_target=False):
+        import make_synthetic_dataset as MS
+        import nerf
+        from launch import common as CM
+        cfgd = MS.config("unused", "unused", num_random_rays=N_RAYS, model_type=model_type)
+        cfgd["nerf"]["train"].update(num_coarse=8, num_fine=8)
+        self.cfg = nerf.CfgNode(cfgd)
+        torch.manual_seed(7)
+        self.model_c, self.model_f = CM.build_models(self.cfg, gpu)
+        self.model_c.train(), self.model_f.train()
+        g = torch.Generator().manual_seed(11)
+        self.latent = torch.zeros(N_FRAMES, 32, device=gpu, requires_grad=True)
+        self.background = (torch.zeros(SIZE, SIZE, 3) if constant_target else torch.rand(SIZE, SIZE, 3, generator=g)).to(gpu)
+        self.background.requires_grad_(train_background)
+        groups = [{"params": list(self.model_c.parameters()) + list(self.model_f.parameters()) + [self.latent]},
+                  {"params": self.background, "lr": LR0}]
+        self.opt = nerf.optim.Adam(groups, lr=LR0, capturable=True)
+        self.opt.set_lr_schedule(LR0, DECAY_FACTOR, DECAY_STEPS)
+        self.poses = [torch.tensor(MS.frame_pose(f), dtype=torch.float32)[:3, :4].contiguous().to(gpu) for f in range(N_FRAMES)]
+        self.exprs = [(0.5 * torch.randn(76, generator=g)).to(gpu) for _ in range(N_FRAMES)]
+        self.imgs = [(torch.full((SIZE, SIZE, 3), 0.5) if constant_target else torch.rand(SIZE, SIZE, 3, generator=g)).to(gpu)
+                     for f in range(N_FRAMES)]
+        self.maps = [(torch.rand(SIZE * SIZE, generator=g) + 0.1).to(gpu) for _ in range(N_FRAMES)]
+        self.rows = torch.arange(N_FRAMES, device=gpu)
+        self.enc = (nerf.get_embedding_function(10, True, True), nerf.get_embedding_function(4, False, True))
+        self.supervised = train_background
+
+    def eager_step(self, k):
+        """The loop body of launch/train_sharded.py (with the background term, when asked for, inside nerf.training_loss)."""
+        import nerf
+        latent = self.latent[k]
+        sel = nerf.choose_rays(self.maps[k], N_RAYS)
+        ro, rd, target, bg = nerf.get_ray_batch(SIZE, SIZE, INTRINSICS, self.poses[k], sel, self.imgs[k], self.background)
+        rgb_c, _, _, rgb_f, _, _, w_last = nerf.run_one_iter_of_nerf(
+            SIZE, SIZE, INTRINSICS, self.model_c, self.model_f, ro, rd, self.cfg, mode="train", encode_position_fn=self.enc[0],
+            encode_direction_fn=self.enc[1], expressions=self.exprs[k], background_prior=bg, latent_code=latent)
+        term = dict(background=bg[..., :3], last_weight=w_last) if self.supervised else {}
+        loss, parts = nerf.training_loss(rgb_c[..., :3], rgb_f[..., :3], target[..., :3], latent, **term)
+        loss.backward()
+        self.opt.step()
+        self.opt.zero_grad()
+        return parts.clone()
+
+    def trainer(self, precision):
+        import nerf
+        return nerf.GraphedTrainer(self.model_c, self.model_f, self.latent, self.background, self.opt, SIZE, SIZE, INTRINSICS, self.cfg,
+                                   precision, supervised_background=self.supervised)
+
+    def graph_step(self, tr, k):
+        tr.step(self.poses[k], self.exprs[k], self.imgs[k], self.maps[k], self.rows[k])
+        return tr.parts.clone()
+
+    def snapshot(self):
+        out = [p.detach().clone() for g in self.opt.param_groups for p in g["params"]]
+        for g in self.opt.param_groups:
+            for p in g["params"]:
+                st = self.opt.state.get(p) or {}
+                out += [st[n].clone() for n in ("exp_avg", "exp_avg_sq") if n in st]
+        return out
+
+
+PAPER, LCODE = "ConditionalBlendshapePaperNeRFModel", "ConditionalBlendshapeLearnableCodeNeRFModel"
+FRAME_ORDER = [0, 2, 1, 1, 0]
+
+
+@pytest.mark.parametrize("model_type,precision", [(PAPER, "f32"), (PAPER, "f16x3"), (LCODE, "f32")])
+def test_graphed_steps_equal_eager_steps(hip_lib, gpu, model_type, precision):
+    """5 steps through nerf.GraphedTrainer and 5 through the eager loop body, from the same seed, frame order and capturable optimizer:
+    parameters, latent table, background, Adam moments and the loss terms are torch.equal after every step -- the same kernels run in
+    the same order on the same inputs, and no kernel of the step accumulates with floating-point atomics (the library's atomics are
+    integer counters; torch's index_add_ / index_put_ in the two scatter backwards touch every destination once)."""
+    import nerf
+    nerf.set_mlp_precision(precision)
+    eager, graphed = _Run(gpu, model_type), _Run(gpu, model_type)
+    for a, b in zip(eager.snapshot(), graphed.snapshot()):
+        assert torch.equal(a, b)
+    torch.manual_seed(123)
+    want = []
+    for k in FRAME_ORDER:
+        parts = eager.eager_step(k)
+        want.append((parts, eager.snapshot()))
+    torch.manual_seed(123)
+    tr = graphed.trainer(precision)
+    for step, k in enumerate(FRAME_ORDER):
+        parts = graphed.graph_step(tr, k)
+        got = graphed.snapshot()
+        assert torch.equal(parts[:7], want[step][0][:7]), (step, parts, want[step][0])
+        assert len(got) == len(want[step][1])
+        for i, (a, b) in enumerate(zip(got, want[step][1])):
+            assert torch.equal(a, b), (step, i, float((a - b).abs().max()))
+    assert float(graphed.opt.state[graphed.latent]["step"]) == 5.0
+    assert bool(torch.isfinite(tr.parts[:7]).all()) and float(graphed.latent.detach().abs().sum()) > 0
+    sel = tr.selected                                                     # the pixels of the last replay, for the launcher's report
+    assert sel.dtype == torch.int64 and sel.shape == (N_RAYS,) and int(sel.min()) >= 0 and int(sel.max()) < SIZE * SIZE
+    assert bool((sel[1:] > sel[:-1]).all())
+    tr.check_range()                                                      # polls the split-fp16 flag outside the graph (no-op for f32)
+    sd = graphed.opt.state_dict()                                         # torch's layout, and the rate the schedule has reached
+    assert all(float(st["step"]) == 5.0 and not st["step"].is_cuda for st in sd["state"].values())
+    assert sd["param_groups"][0]["lr"] == LR0 * DECAY_FACTOR ** (4.0 / DECAY_STEPS)
+    with pytest.raises(ValueError, match="captured graph was built for"):
+        tr.step(graphed.poses[0], graphed.exprs[0], graphed.imgs[0][:16], graphed.maps[0], graphed.rows[0])
+
+
+def test_replays_touch_only_the_frames_row_and_train(hip_lib, gpu):
+    """20 replays, frames cycling 0, 1, 2, constant-colour targets.  What a step does to the latent rows of the frames it did NOT use:
+    their gradient is exactly zero, so a row no step has used yet is bitwise unchanged, and a row used before moves exactly as one
+    Adam step on a zero gradient moves it (dense Adam keeps applying the decaying first moment -- the eager loop and the reference
+    do the same; `bitwise unchanged` can only hold while the row's moments are still zero).  The loss is finite and lower at step 20
+    than at step 1."""
+    from nerf import _hip as H
+    run = _Run(gpu, PAPER, constant_target=True)
+    torch.manual_seed(5)
+    tr = run.trainer("f32")
+    losses = []
+    n = (C.c_int64 * 1)(32)
+    for step in range(20):
+        k = step % 3
+        st = run.opt.state.get(run.latent) or {}
+        before = run.latent.detach().clone()
+        m0 = st["exp_avg"].clone() if st else torch.zeros_like(before)
+        v0 = st["exp_avg_sq"].clone() if st else torch.zeros_like(before)
+        losses.append(float(run.graph_step(tr, k)[0]))
+        for r in range(3):
+            if r == k:
+                continue
+            if step < r:                                                  # frame r has not been used yet: nothing moves
+                assert torch.equal(run.latent[r], before[r])
+                continue
+            p, m, v, g = before[r].clone(), m0[r].clone(), v0[r].clone(), torch.zeros(32, device=gpu)
+            one = lambda t: (C.c_void_p * 1)(int(t.data_ptr()))
+            lr = _device_lr(step)
+            H.check(hip_lib.nf_adam_step(one(p), one(g), one(m), one(v), n, 1, lr, 0.9, 0.999, 1e-8, step + 1, H.stream_ptr(gpu)),
+                    "nf_adam_step")
+            assert torch.equal(run.latent[r].detach(), p), (step, r)
+            assert torch.equal(run.opt.state[run.latent]["exp_avg"][r], m) and torch.equal(run.opt.state[run.latent]["exp_avg_sq"][r], v)
+        assert not torch.equal(run.latent[k], before[k])                  # the frame's own row did train
+    assert all(np.isfinite(l) for l in losses) and losses[19] < losses[0], losses
+
+
+def test_supervised_background_under_capture_equals_eager(hip_lib, gpu):
+    """3 steps with a background that requires grad and the term of TR:376-381 inside the fused loss: the background (the optimizer's
+    second group), its moments and everything else equal the eager loop's; the term is reported as parts[7].
+    The eager side here calls nerf.training_loss(background=, last_weight=) too, i.e. the same fused kernels, on purpose: what this
+    test pins down is that the CAPTURE changes nothing.  launch/train_sharded.py without --graph keeps building the term from six
+    torch ops; the two formulations agree to float32 rounding of the term and its gradients (both are held to float64 in
+    test_train_loss_bg_matches_float64_autograd, the kernels at 3.8e-7, torch's ops measure 1.9e-7), not bit for bit, so a
+    --graph run and a run without it are not compared bitwise with a supervised background."""
+    eager, graphed = _Run(gpu, PAPER, train_background=True), _Run(gpu, PAPER, train_background=True)
+    bg0 = eager.background.detach().clone()
+    torch.manual_seed(77)
+    want = []
+    for k in (0, 1, 2):
+        parts = eager.eager_step(k)
+        want.append((parts, eager.snapshot()))
+    assert not torch.equal(eager.background.detach(), bg0)
+    torch.manual_seed(77)
+    tr = graphed.trainer("f32")
+    for step, k in enumerate((0, 1, 2)):
+        parts = graphed.graph_step(tr, k)
+        assert torch.equal(parts, want[step][0]) and float(parts[7]) > 0.0
+        for a, b in zip(graphed.snapshot(), want[step][1]):
+            assert torch.equal(a, b)
+    assert torch.equal(graphed.background.detach(), eager.background.detach())
+    assert float(graphed.opt.state[graphed.background]["step"]) == 3.0
+
+
+# ------------------------------------------------------------------------------------------------------- the launcher
+def test_launcher_graph_switch_and_checkpoint_exchange(hip_lib, gpu, tmp_path):
+    """launch.train_sharded.main([..., "--graph"]): 6 iterations at 32 x 32, 64 rays, a checkpoint at iteration 5 in the usual
+    dictionary; it loads with --load-checkpoint into a run WITHOUT --graph, which continues -- and the other way round."""
+    import make_synthetic_dataset as MS
+    from launch import train_sharded
+    base = str(tmp_path)
+    MS.write(os.path.join(base, "data"))
+    cfg_path = os.path.join(base, "config.yml")
+    cfg = MS.config(os.path.join(base, "data"), os.path.join(base, "logs"), num_random_rays=N_RAYS)
+    cfg["experiment"]["validate_every"] = 4
+    yaml.safe_dump(cfg, open(cfg_path, "w"))
+    logdir = train_sharded.main(["--config", cfg_path, "--graph"])
+    ck_path = os.path.join(logdir, "checkpoint00005.ckpt")
+    ck = torch.load(ck_path, map_location="cpu")
+    assert set(ck) == {"iter", "model_coarse_state_dict", "model_fine_state_dict", "optimizer_state_dict", "loss", "psnr", "background",
+                       "latent_codes"}
+    assert ck["iter"] == 5 and np.isfinite(float(ck["loss"])) and float(ck["latent_codes"].abs().sum()) > 0
+    steps = {float(st["step"]) for st in ck["optimizer_state_dict"]["state"].values()}
+    assert steps == {6.0} and all(not st["step"].is_cuda for st in ck["optimizer_state_dict"]["state"].values())
+    assert [g["lr"] for g in ck["optimizer_state_dict"]["param_groups"]] == [5.0e-4 * 0.1 ** (5 / 250000)] * 2    # as the eager loop leaves both
+    cfg["experiment"]["train_iters"] = 8
+    yaml.safe_dump(cfg, open(cfg_path, "w"))
+    train_sharded.main(["--config", cfg_path, "--load-checkpoint", ck_path])                          # graph -> eager
+    ck2_path = os.path.join(logdir, "checkpoint00007.ckpt")
+    ck2 = torch.load(ck2_path, map_location="cpu")
+    assert not torch.equal(ck2["latent_codes"], ck["latent_codes"]) and np.isfinite(float(ck2["loss"]))
+    assert {float(st["step"]) for st in ck2["optimizer_state_dict"]["state"].values()} == {9.0}
+    cfg["experiment"]["train_iters"] = 10
+    yaml.safe_dump(cfg, open(cfg_path, "w"))
+    train_sharded.main(["--config", cfg_path, "--load-checkpoint", ck2_path, "--graph"])              # eager -> graph
+    ck3 = torch.load(os.path.join(logdir, "checkpoint00009.ckpt"), map_location="cpu")
+    assert {float(st["step"]) for st in ck3["optimizer_state_dict"]["state"].values()} == {12.0}
+    assert np.isfinite(float(ck3["loss"])) and not torch.equal(ck3["latent_codes"], ck2["latent_codes"])
