@@ -136,7 +136,7 @@ k_lcode_mlp_fwd(const float* __restrict__ packed, const float* __restrict__ cond
         dirf[t][0] = (f32x4){s, cs, 0.0f, 0.0f};
     }
     f32x4 acc[NT][16];
-    // Layer-streamed form (nf_mlp_stream.h; the paper model's k_paper_mlp_fwd is the template).  layers_xyz.2's output feeds fc_alpha AND
+    // Layer-streamed form (nf_mlp_stream.h; same form as the paper model's nf_paper_net_body, nf_mlp_paper_net.h).  layers_xyz.2's output feeds fc_alpha AND
     // fc_feat: fc_alpha's tail stores nothing (NO_ST = 0), so fc_feat reads the same slab again.
     NfStream<NT> st;
     f32x4 bj[NT];
@@ -346,8 +346,8 @@ int nf_lcode_launch_fwd_encoded(const float* packed, const float* cond, const fl
 }
 
 // Training forward (exact f32): the same arithmetic plus `saved` (layout nlc::S_*) -- every layer output as whole rows out of the
-// wave's LDS slab from inside the next layer's K loop, ReLU bit masks beside them (nf_mlp_dev.h, nf_mlp_stream.h; the paper model's
-// k_paper_mlp_fwd_save is the template).
+// wave's LDS slab from inside the next layer's K loop, ReLU bit masks beside them (nf_mlp_dev.h, nf_mlp_stream.h; the same form as
+// the paper model's nf_paper_net_body_save, nf_mlp_paper_net.h).
 template <int NT>
 __global__ void __launch_bounds__(64 * NF_MLP_WAVES, 1)
 k_lcode_mlp_fwd_save(const float* __restrict__ packed, const float* __restrict__ cond, const float* __restrict__ ro,
