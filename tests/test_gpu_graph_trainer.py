@@ -21,9 +21,10 @@ LR0, DECAY_FACTOR, DECAY_STEPS = 5.0e-4, 0.1, 10.0            # a schedule that 
 
 
 # ------------------------------------------------------------------------------------------------------- nf_adam_step_dev
-def _device_lr(step_done):
+def _device_lr(step_done, lr0=LR0, factor=DECAY_FACTOR, steps=DECAY_STEPS):
     s = np.float64(np.float32(step_done))
-    return float(np.float32(LR0 if s == 0.0 else np.float64(LR0) * np.power(np.float64(DECAY_FACTOR), (s - 1.0) / np.float64(DECAY_STEPS))))
+    with np.errstate(under="ignore"):
+        return float(np.float32(lr0 if s == 0.0 else np.float64(lr0) * np.power(np.float64(factor), (s - 1.0) / np.float64(steps))))
 
 
 def test_adam_step_dev_equals_the_host_scalar_kernel_bit_for_bit(hip_lib, gpu):
@@ -56,6 +57,87 @@ def test_adam_step_dev_equals_the_host_scalar_kernel_bit_for_bit(hip_lib, gpu):
         assert torch.equal(a, b)
     assert float(state[0]) == 4.0 and int(state.view(torch.int32)[1]) == 0
     assert hip_lib.nf_adam_step_dev(arr(p_dev), arr(grads[0]), arr(m_dev), arr(v_dev), numel, n, 0.9, 0.999, 1e-8, 0, s) != 0   # no state block
+
+
+# the schedule of this file (at a count of 10^6 its rate has underflowed to exactly 0: the moments still move, the parameters must not)
+# and the one the launcher's configs set (lr_decay 250 x 1000 steps: 5.0e-8 at 10^6, so the parameters move there too)
+SCHEDULES = {"file": (LR0, DECAY_FACTOR, DECAY_STEPS), "launcher": (5.0e-4, 0.1, 250000.0)}
+
+
+def _state_block(gpu, step, schedule):
+    state = torch.zeros(8, dtype=torch.float32, device=gpu)
+    state[0] = float(step)
+    state[2:8].view(torch.float64).copy_(torch.tensor(schedule, dtype=torch.float64))
+    return state
+
+
+@pytest.mark.parametrize("schedule", sorted(SCHEDULES))
+@pytest.mark.parametrize("step0", [9, 10, 11, 999999, 2 ** 24 - 2])
+def test_adam_step_dev_from_a_preloaded_step_count(hip_lib, gpu, step0, schedule):
+    """The state block preloaded with the count a resumed run starts from: around the first decay period of this file's schedule
+    (9, 10, 11), the host kernel's largest tested count (999 999 -> step 10^6) and the last count at which float32 `step + 1` is
+    exact (2^24 - 2).  The 5 tensor sizes of the test above, non-zero moments, 2 consecutive steps: parameters and both moments equal
+    nf_adam_step fed lr = _device_lr(step) and step + 1; the block's step reads back step0 + 2 and its ticket 0."""
+    from nerf import _hip as H
+    sched = SCHEDULES[schedule]
+    g = torch.Generator().manual_seed(5 + step0 % 1000)
+    sizes = (1, 63, 64, 257, 70001)
+    mk = lambda scale=1.0: [(scale * torch.randn(n, generator=g)).to(gpu) for n in sizes]
+    p_ref, grads = mk(0.1), [mk() for _ in range(2)]
+    m_ref, v_ref = mk(0.01), [(1e-4 * torch.rand(n, generator=g)).to(gpu) for n in sizes]
+    p0, m0 = [p.clone() for p in p_ref], [m.clone() for m in m_ref]
+    p_dev, m_dev, v_dev = ([t.clone() for t in ts] for ts in (p_ref, m_ref, v_ref))
+    state = _state_block(gpu, step0, sched)
+    n = len(sizes)
+    arr = lambda ts: (C.c_void_p * n)(*[int(t.data_ptr()) for t in ts])
+    numel = (C.c_int64 * n)(*sizes)
+    s = H.stream_ptr(gpu)
+    for k in range(2):
+        lr = _device_lr(step0 + k, *sched)
+        H.check(hip_lib.nf_adam_step(arr(p_ref), arr(grads[k]), arr(m_ref), arr(v_ref), numel, n, lr, 0.9, 0.999, 1e-8, step0 + k + 1, s),
+                "nf_adam_step")
+        H.check(hip_lib.nf_adam_step_dev(arr(p_dev), arr(grads[k]), arr(m_dev), arr(v_dev), numel, n, 0.9, 0.999, 1e-8,
+                                         int(state.data_ptr()), s), "nf_adam_step_dev")
+        assert float(state[0]) == float(step0 + k + 1) and int(state.view(torch.int32)[1]) == 0
+    for i, (a, b) in enumerate(zip(p_ref + m_ref + v_ref, p_dev + m_dev + v_dev)):
+        assert torch.equal(a, b), (step0, schedule, i, int((a != b).sum()))
+    assert float(state[0]) == float(step0 + 2)
+    if _device_lr(step0, *sched) == 0.0:
+        assert all(torch.equal(a, b) for a, b in zip(p_dev, p0))          # a rate of exactly 0 leaves the parameters alone
+    else:
+        assert all(not torch.equal(a, b) for a, b in zip(p_dev[1:], p0[1:]))
+    assert all(not torch.equal(a, b) for a, b in zip(m_dev[1:], m0[1:]))
+
+
+@pytest.mark.parametrize("schedule", sorted(SCHEDULES))
+def test_adam_step_dev_at_a_million_steps_against_float64(hip_lib, gpu, schedule):
+    """One 257-element tensor, the state block preloaded with 999 999: the update restated in numpy float64 from the same float32
+    inputs (m, v, the bias corrections of step 10^6, the rate of the schedule) -- tests/test_gpu_small_kernels.py's _adam_reference.
+    The bound is the one that file holds nf_adam_step to at step 10^6: the kernel's p, m and v are bit-equal to the float32
+    evaluation of the same three lines (one correctly rounded numpy operation at a time), i.e. its error against float64 is 1.000 x
+    the float32 evaluation's.  Both errors are printed."""
+    from nerf import _hip as H
+    from tests.test_gpu_small_kernels import _adam_constants, _adam_reference, _adam_tensor
+    sched = SCHEDULES[schedule]
+    t = _adam_tensor(257, 4242)
+    lr = _device_lr(999999, *sched)
+    assert (lr == 0.0) == (schedule == "file")
+    c64, c32 = _adam_constants(10 ** 6, lr=lr)
+    ref64 = _adam_reference(t["p"], t["g"], t["m"], t["v"], c64, torch.float64)
+    ref32 = _adam_reference(t["p"], t["g"], t["m"], t["v"], c32, torch.float32)
+    dev = {r: t[r].to(gpu) for r in "pgmv"}
+    state = _state_block(gpu, 999999, sched)
+    one = lambda x: (C.c_void_p * 1)(int(x.data_ptr()))
+    H.check(hip_lib.nf_adam_step_dev(one(dev["p"]), one(dev["g"]), one(dev["m"]), one(dev["v"]), (C.c_int64 * 1)(257), 1, 0.9, 0.999, 1e-8,
+                                     int(state.data_ptr()), H.stream_ptr(gpu)), "nf_adam_step_dev")
+    assert float(state[0]) == 1.0e6 and int(state.view(torch.int32)[1]) == 0
+    for r, r64, r32 in zip("pmv", ref64, ref32):
+        got = dev[r].cpu()
+        e_k, e_32 = float((got.double() - r64).abs().max()), float((r32.double() - r64).abs().max())
+        print(f"{schedule} {r}: device error against float64 {e_k:.3e}, float32 evaluation {e_32:.3e}")
+        assert torch.equal(got.view(torch.int32), r32.view(torch.int32)), (r, int((got != r32).sum()), e_k, e_32)
+        assert e_k <= e_32
+    assert (schedule == "file") == torch.equal(dev["p"].cpu(), t["p"])     # the parameters move exactly when the rate is not 0
 
 
 def test_adam_step_dev_table_split_over_several_launches(hip_lib, gpu):
@@ -165,27 +247,44 @@ def test_training_loss_without_the_term_is_todays(hip_lib, gpu, fine):
 
 # ------------------------------------------------------------------------------------------------------- graph against eager
 class _Run:
-    """Models, latent table, background, capturable optimizer and 3 frames, built the same way from a seed."""
+    """Models, latent table, background, optimizer and 3 frames, built the same way from a seed.  The keyword arguments switch what
+    the launcher's users can switch; their defaults are the run every test of this file started from:
+      capturable=False   the launcher's loop without --graph: the host-stepped nerf.optim.Adam, `lr` rewritten on the host after each step
+      background=False   no background prior: one param group, no `bg` gather
+      train_cfg/val_cfg  entries of cfg.nerf.train / cfg.nerf.validation (chunksize, num_fine, white_background, lindisp, perturb, ...)
+      pose44             poses handed over as (4, 4) instead of (3, 4)
+      latent_std         rows of the latent table drawn N(0, latent_std^2) (from a generator of their own) instead of zero"""
 
-    def __init__(self, gpu, model_type, train_background=False, constant_target=False):
+    def __init__(self, gpu, model_type, train_background=False, constant_target=False, *, capturable=True, background=True,
+                 train_cfg=None, val_cfg=None, pose44=False, latent_std=0.0):
         import make_synthetic_dataset as MS
         import nerf
         from launch import common as CM
         cfgd = MS.config("unused", "unused", num_random_rays=N_RAYS, model_type=model_type)
         cfgd["nerf"]["train"].update(num_coarse=8, num_fine=8)
+        cfgd["nerf"]["train"].update(train_cfg or {})
+        cfgd["nerf"]["validation"].update(val_cfg or {})
         self.cfg = nerf.CfgNode(cfgd)
         torch.manual_seed(7)
         self.model_c, self.model_f = CM.build_models(self.cfg, gpu)
         self.model_c.train(), self.model_f.train()
         g = torch.Generator().manual_seed(11)
-        self.latent = torch.zeros(N_FRAMES, 32, device=gpu, requires_grad=True)
+        self.latent = torch.zeros(N_FRAMES, 32, device=gpu)
+        if latent_std:
+            self.latent += (latent_std * torch.randn(N_FRAMES, 32, generator=torch.Generator().manual_seed(13))).to(gpu)
+        self.latent.requires_grad_(True)
         self.background = (torch.zeros(SIZE, SIZE, 3) if constant_target else torch.rand(SIZE, SIZE, 3, generator=g)).to(gpu)
         self.background.requires_grad_(train_background)
         groups = [{"params": list(self.model_c.parameters()) + list(self.model_f.parameters()) + [self.latent]},
                   {"params": self.background, "lr": LR0}]
-        self.opt = nerf.optim.Adam(groups, lr=LR0, capturable=True)
-        self.opt.set_lr_schedule(LR0, DECAY_FACTOR, DECAY_STEPS)
-        self.poses = [torch.tensor(MS.frame_pose(f), dtype=torch.float32)[:3, :4].contiguous().to(gpu) for f in range(N_FRAMES)]
+        if not background:
+            self.background, groups = None, groups[:1]
+        self.capturable = capturable
+        self.opt = nerf.optim.Adam(groups, lr=LR0, capturable=capturable)
+        if capturable:
+            self.opt.set_lr_schedule(LR0, DECAY_FACTOR, DECAY_STEPS)
+        rows = 4 if pose44 else 3
+        self.poses = [torch.tensor(MS.frame_pose(f), dtype=torch.float32)[:rows, :4].contiguous().to(gpu) for f in range(N_FRAMES)]
         self.exprs = [(0.5 * torch.randn(76, generator=g)).to(gpu) for _ in range(N_FRAMES)]
         self.imgs = [(torch.full((SIZE, SIZE, 3), 0.5) if constant_target else torch.rand(SIZE, SIZE, 3, generator=g)).to(gpu)
                      for f in range(N_FRAMES)]
@@ -193,6 +292,7 @@ class _Run:
         self.rows = torch.arange(N_FRAMES, device=gpu)
         self.enc = (nerf.get_embedding_function(10, True, True), nerf.get_embedding_function(4, False, True))
         self.supervised = train_background
+        self.steps_done = 0                                               # the launcher's `i`, for the rate a host-stepped loop writes
 
     def eager_step(self, k):
         """The loop body of launch/train_sharded.py (with the background term, when asked for, inside nerf.training_loss)."""
@@ -204,10 +304,14 @@ class _Run:
             SIZE, SIZE, INTRINSICS, self.model_c, self.model_f, ro, rd, self.cfg, mode="train", encode_position_fn=self.enc[0],
             encode_direction_fn=self.enc[1], expressions=self.exprs[k], background_prior=bg, latent_code=latent)
         term = dict(background=bg[..., :3], last_weight=w_last) if self.supervised else {}
-        loss, parts = nerf.training_loss(rgb_c[..., :3], rgb_f[..., :3], target[..., :3], latent, **term)
+        loss, parts = nerf.training_loss(rgb_c[..., :3], rgb_f[..., :3] if rgb_f is not None else None, target[..., :3], latent, **term)
         loss.backward()
         self.opt.step()
         self.opt.zero_grad()
+        if not self.capturable:                                           # the launcher's lr_new, written into every group after step i
+            for g in self.opt.param_groups:
+                g["lr"] = LR0 * DECAY_FACTOR ** (self.steps_done / DECAY_STEPS)
+        self.steps_done += 1
         return parts.clone()
 
     def trainer(self, precision):
