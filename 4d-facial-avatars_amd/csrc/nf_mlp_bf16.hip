@@ -29,39 +29,33 @@
 
 static void nf_build_table_bf16(std::vector<uint32_t>& t) {
     using namespace nfb;
-    t.assign((size_t)N_PAIRS * 512, NF_ZERO_CODE);
     // per layer: tensor id of the weight, its column count, and the slot -> column rule
-    for (int l = 0; l < NL; ++l) {
-        for (int s = 0; s < KS[l]; ++s)
-            for (int nt = 0; nt < NO[l]; ++nt)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int j = 0; j < 8; ++j) {
-                        const int h = lane >> 5, i = lane & 31, n = 32 * nt + i;
-                        uint32_t c = NF_ZERO_CODE;
-                        switch (l) {
-                            case 0: { const int col = pe_col(s, h, j); if (col >= 0) c = nf_code(0, n, col, 171); } break;
-                            case 1: c = nf_code(2, n, hid_feature(s, h, j), 256); break;
-                            case 2: c = nf_code(4, n, hid_feature(s, h, j), 256); break;
-                            case 3: {
-                                if (s < 4) { const int col = pe_col(s, h, j); if (col >= 0) c = nf_code(6, n, col, 427); }
-                                else c = nf_code(6, n, 171 + hid_feature(s - 4, h, j), 427);
-                            } break;
-                            case 4: c = nf_code(8, n, hid_feature(s, h, j), 256); break;
-                            case 5: c = nf_code(10, n, hid_feature(s, h, j), 256); break;
-                            case 6: c = nf_code(12, n, hid_feature(s, h, j), 256); break;
-                            case 7: {   // layers_dir.0 (+ fc_alpha as row 128); k-steps 0..15 feat, 16 dir slots, 17 zero
-                                if (n < 128) {
-                                    if (s < 16) c = nf_code(16, n, hid_feature(s, h, j), 280);
-                                    else if (s == 16) { const int col = dir_col(h, j); if (col >= 0) c = nf_code(16, n, col, 280); }
-                                } else if (n == 128 && s < 16) c = nf_code(14, 0, hid_feature(s, h, j), 256);
-                            } break;
-                            case 8: c = nf_code(18, n, hid_feature(s, h, j), 128); break;
-                            case 9: c = nf_code(20, n, hid_feature(s, h, j), 128); break;
-                            case 10: if (n < 3) c = nf_code(24, n, hid_feature(s, h, j), 128); break;
-                        }
-                        t[((size_t)(pair_off(l) + s * NO[l] + nt)) * 512 + lane * 8 + j] = c;
-                    }
-    }
+    fill_table(t, [](int l, int s, int nt, int h, int i, int j) {
+        const int n = 32 * nt + i;
+        uint32_t c = NF_ZERO_CODE;
+        switch (l) {
+            case 0: { const int col = pe_col(s, h, j); if (col >= 0) c = nf_code(0, n, col, 171); } break;
+            case 1: c = nf_code(2, n, hid_feature(s, h, j), 256); break;
+            case 2: c = nf_code(4, n, hid_feature(s, h, j), 256); break;
+            case 3: {
+                if (s < 4) { const int col = pe_col(s, h, j); if (col >= 0) c = nf_code(6, n, col, 427); }
+                else c = nf_code(6, n, 171 + hid_feature(s - 4, h, j), 427);
+            } break;
+            case 4: c = nf_code(8, n, hid_feature(s, h, j), 256); break;
+            case 5: c = nf_code(10, n, hid_feature(s, h, j), 256); break;
+            case 6: c = nf_code(12, n, hid_feature(s, h, j), 256); break;
+            case 7: {   // layers_dir.0 (+ fc_alpha as row 128); k-steps 0..15 feat, 16 dir slots, 17 zero
+                if (n < 128) {
+                    if (s < 16) c = nf_code(16, n, hid_feature(s, h, j), 280);
+                    else if (s == 16) { const int col = dir_col(h, j); if (col >= 0) c = nf_code(16, n, col, 280); }
+                } else if (n == 128 && s < 16) c = nf_code(14, 0, hid_feature(s, h, j), 256);
+            } break;
+            case 8: c = nf_code(18, n, hid_feature(s, h, j), 128); break;
+            case 9: c = nf_code(20, n, hid_feature(s, h, j), 128); break;
+            case 10: if (n < 3) c = nf_code(24, n, hid_feature(s, h, j), 128); break;
+        }
+        return c;
+    });
 }
 
 void nf_build_table_bf16_shared(std::vector<uint32_t>& t) { nf_build_table_bf16(t); }      // also the split-fp16 stream's table

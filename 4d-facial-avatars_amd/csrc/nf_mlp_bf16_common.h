@@ -9,7 +9,8 @@ namespace nfb {
 constexpr int NL = 11;
 constexpr int KS[NL] = {4, 16, 16, 20, 16, 16, 16, 18, 8, 8, 8};   // multiples of the stage depth (2 k-steps); layers_dir.0: 16 feat + dir + ONE zero k-step (round 5: 3)
 constexpr int NO[NL] = {8, 8, 8, 8, 8, 8, 8, 5, 4, 4, 1};
-constexpr int pair_off(int l) { int o = 0; for (int i = 0; i < l; ++i) o += KS[i] * NO[i]; return o; }
-constexpr int N_PAIRS = pair_off(NL);                 // (hi, lo) 1-KiB block pairs
-constexpr int STREAM_BF16 = N_PAIRS * 2 * 512;        // bf16 elements
 }  // namespace nfb
+#include "nf_mlp_split_table.h"
+
+// the sections of `saved` the shared forward text writes (nf_mlp_split_fwd.inc)
+struct NfbSections { static constexpr int S_PE = nfl::S_PE, S_DIRF = nfl::S_DIRF, S_MASK = nfl::S_MASK; };

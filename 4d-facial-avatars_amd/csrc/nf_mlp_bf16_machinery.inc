@@ -1,6 +1,7 @@
 // Table-driven machinery of the split-bf16 fused MLP kernels (weight-stream -> LDS ring, stage/layer drivers, operand split,
-// activation saves).  Included by the forward (nf_mlp_bf16_kernel.inc) and backward-chain (nf_mlp_bf16_bwd.hip) kernels after
-// nf_mlp_split_common.h and a header that defines namespace nfb { NL, KS[], NO[], pair_off() } for THEIR weight stream.
+// activation saves).  Included by the forward (nf_mlp_*bf16_kernel.inc) and backward-chain (nf_mlp_*bf16_bwd.hip) kernels of both
+// families after nf_mlp_split_common.h and the layer table namespace nfb { NL, KS[], NO[] } of THEIR weight stream with what
+// nf_mlp_split_table.h derives from it.  The kernel text the families share: nf_mlp_split_fwd.inc, nf_mlp_split_bwd.inc.
 // =================================================================================================
 // forward
 // =================================================================================================
@@ -480,6 +481,17 @@ __device__ __forceinline__ void nfb_flush_layer_max(const float (&lm)[N], unsign
 }
 #endif
 
+// backward chain: d sigma joins the operands (th, tl) as k-step S, slot (0, 0) of the lanes that are `on`, at the scale g of the
+// k-steps in front of it; k-step S + 1 is zero
+template <int S>
+__device__ __forceinline__ void nfb_dsigma_kstep(bf16x8 (&th)[20], bf16x8 (&tl)[20], bool on, float d_sigma, float g) {
+    float x[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if (on) x[0] = d_sigma * g;
+    nfb_split(x, th[S], tl[S]);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) { th[S + 1][j] = (nfb_elt)0.f; tl[S + 1][j] = (nfb_elt)0.f; }
+}
+
 template <int NO>
 __device__ __forceinline__ void nfb_scale(f32x16 (&acc)[8], float s) {
 #pragma unroll
@@ -503,5 +515,23 @@ __device__ __forceinline__ void nfb_init_bias(f32x16 (&acc)[8], const float* bia
 __device__ __forceinline__ void nfb_zero(f32x16& a) {
 #pragma unroll
     for (int r = 0; r < 16; ++r) a[r] = 0.f;
+}
+
+template <int NO>
+__device__ __forceinline__ void nfb_zero_tiles(f32x16 (&acc)[8]) {
+#pragma unroll
+    for (int nt = 0; nt < NO; ++nt) nfb_zero(acc[nt]);
+}
+
+// backward chain: acc[nt] reg r keeps its value where bit (16 nt + r) of the lane's 128-bit ReLU mask (nfb_save_mask) is set
+template <int NO>
+__device__ __forceinline__ void nfb_apply_mask(f32x16 (&acc)[8], const nfb_u32x4& m) {
+#pragma unroll
+    for (int nt = 0; nt < NO; ++nt)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const unsigned bit = (m[nt >> 1] >> (16 * (nt & 1) + r)) & 1u;
+            acc[nt][r] = bit ? acc[nt][r] : 0.0f;
+        }
 }
 

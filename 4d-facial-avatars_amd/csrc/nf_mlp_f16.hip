@@ -27,10 +27,8 @@ static NfPackTable g_paper_table_h;
 extern "C" size_t nf_paper_packed_f16_bytes(void) { return (size_t)nfb::STREAM_BF16 * 2 + NF_F16_TAIL_BYTES; }
 
 extern "C" int nf_paper_pack_f16(const float* const* params, void* stream_out, nf_stream_t stream) {
-    NfLayerPairs<nfb::NL> lp;
-    for (int l = 0; l <= nfb::NL; ++l) lp.off[l] = nfb::pair_off(l);
     return nf_pack_split_f16<NF_PAPER_NUM_PARAMS, 7, nfb::NL>(g_paper_table_h, nf_build_table_bf16_shared, params, stream_out,
-                                                              nfb::N_PAIRS * 512, lp, (float)(1 << NFB_ACT_SHIFT), stream);
+                                                              nfb::N_PAIRS * 512, nfb::layer_pairs(), (float)(1 << NFB_ACT_SHIFT), stream);
 }
 
 #define NFB_SAVE 0

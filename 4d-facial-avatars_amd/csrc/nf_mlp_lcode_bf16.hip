@@ -18,29 +18,24 @@
 void nf_lcode_build_table_bf16(std::vector<uint32_t>& t, const NfLcodeGeom& ge) {
     using namespace nfb;
     const int* id = ge.id;
-    t.assign((size_t)N_PAIRS * 512, NF_ZERO_CODE);
-    for (int l = 0; l < NL; ++l)
-        for (int s = 0; s < KS[l]; ++s)
-            for (int nt = 0; nt < NO[l]; ++nt)
-                for (int lane = 0; lane < 64; ++lane)
-                    for (int j = 0; j < 8; ++j) {
-                        const int h = lane >> 5, i = lane & 31, n = 32 * nt + i;
-                        uint32_t c = NF_ZERO_CODE;
-                        switch (l) {
-                            case 0: { const int col = pe_col(s, h, j); if (col >= 0) c = nf_code(id[0], n, col, ge.ld1); } break;
-                            case 1: c = nf_code(id[2], n, hid_feature(s, h, j), 256); break;
-                            case 2: c = nf_code(id[4], n, hid_feature(s, h, j), 256); break;
-                            case 3: c = nf_code(id[6], n, hid_feature(s, h, j), 256); break;
-                            case 4: if (n == 0) c = nf_code(id[10], 0, hid_feature(s, h, j), 256); break;
-                            case 5: c = nf_code(id[14], n, hid_feature(s, h, j), 256); break;
-                            case 6:
-                                if (s < 16) c = nf_code(id[8], n, hid_feature(s, h, j), 280);
-                                else if (s == 16) { const int col = dir_col(h, j); if (col >= 0) c = nf_code(id[8], n, col, 280); }
-                                break;
-                            case 7: if (n < 3) c = nf_code(id[12], n, hid_feature(s, h, j), 128); break;
-                        }
-                        t[((size_t)(pair_off(l) + s * NO[l] + nt)) * 512 + lane * 8 + j] = c;
-                    }
+    fill_table(t, [&](int l, int s, int nt, int h, int i, int j) {
+        const int n = 32 * nt + i;
+        uint32_t c = NF_ZERO_CODE;
+        switch (l) {
+            case 0: { const int col = pe_col(s, h, j); if (col >= 0) c = nf_code(id[0], n, col, ge.ld1); } break;
+            case 1: c = nf_code(id[2], n, hid_feature(s, h, j), 256); break;
+            case 2: c = nf_code(id[4], n, hid_feature(s, h, j), 256); break;
+            case 3: c = nf_code(id[6], n, hid_feature(s, h, j), 256); break;
+            case 4: if (n == 0) c = nf_code(id[10], 0, hid_feature(s, h, j), 256); break;
+            case 5: c = nf_code(id[14], n, hid_feature(s, h, j), 256); break;
+            case 6:
+                if (s < 16) c = nf_code(id[8], n, hid_feature(s, h, j), 280);
+                else if (s == 16) { const int col = dir_col(h, j); if (col >= 0) c = nf_code(id[8], n, col, 280); }
+                break;
+            case 7: if (n < 3) c = nf_code(id[12], n, hid_feature(s, h, j), 128); break;
+        }
+        return c;
+    });
 }
 
 static void nf_lcode_table_bf16(std::vector<uint32_t>& t) { nf_lcode_build_table_bf16(t, NF_LCODE_GEOM); }

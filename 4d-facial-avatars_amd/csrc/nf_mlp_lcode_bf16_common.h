@@ -8,7 +8,8 @@ namespace nfb {
 constexpr int NL = 8;
 constexpr int KS[NL] = {4, 16, 16, 16, 16, 16, 18, 8};   // layers_dir.0: 16 feat k-steps + the dir k-step + ONE zero k-step (a stage is 2 k-steps; round 5: 3)
 constexpr int NO[NL] = {8, 8, 8, 8, 1, 8, 4, 1};
-constexpr int pair_off(int l) { int o = 0; for (int i = 0; i < l; ++i) o += KS[i] * NO[i]; return o; }
-constexpr int N_PAIRS = pair_off(NL);
-constexpr int STREAM_BF16 = N_PAIRS * 2 * 512;
 }  // namespace nfb
+#include "nf_mlp_split_table.h"
+
+// the sections of `saved` the shared forward text writes (nf_mlp_split_fwd.inc)
+struct NfbSections { static constexpr int S_PE = nlc::S_PE, S_DIRF = nlc::S_DIRF, S_MASK = nlc::S_MASK; };

@@ -18,15 +18,13 @@ extern "C" size_t nf_lcode_packed_f16_bytes(void) { return (size_t)nfb::STREAM_B
 extern "C" size_t nf_lcode_f16_flag_offset(void) { return (size_t)nfb::STREAM_BF16 * 2 + 4 * NF_F16_FLAG_WORD; }
 
 extern "C" int nf_lcode_pack_f16(const float* const* params, void* stream_out, nf_stream_t stream) {
-    NfLayerPairs<nfb::NL> lp;
-    for (int l = 0; l <= nfb::NL; ++l) lp.off[l] = nfb::pair_off(l);
-    return nf_pack_split_f16<nlc::NPARAMS, 11, nfb::NL>(g_lcode_table_h, nf_lcode_table_bf16_shared, params, stream_out, nfb::N_PAIRS * 512, lp,
-                                              (float)(1 << NFB_ACT_SHIFT), stream);
+    return nf_pack_split_f16<nlc::NPARAMS, 11, nfb::NL>(g_lcode_table_h, nf_lcode_table_bf16_shared, params, stream_out, nfb::N_PAIRS * 512,
+                                                        nfb::layer_pairs(), (float)(1 << NFB_ACT_SHIFT), stream);
 }
 
 // the stream's layer boundaries (NL + 1 pair offsets) and activation pre-scale, for the classes that pack their own tensors into it
 float nf_lcode_f16_stream_layers(int* pair_off) {
-    for (int l = 0; l <= nfb::NL; ++l) pair_off[l] = nfb::pair_off(l);
+    nfb::fill_pair_off(pair_off);
     return (float)(1 << NFB_ACT_SHIFT);
 }
 

@@ -1,6 +1,6 @@
 // Shared by the split-precision kernels of both model families (forward streams, backward chains, weight-gradient GEMMs): the
-// element-type switch, the family-independent slot helpers and the forward launch.  A family's header adds its layer table
-// (namespace nfb { NL, KS[], NO[], pair_off() }).
+// element-type switch, the family-independent slot helpers and the forward and backward-chain launches.  A family's header adds
+// its layer table (namespace nfb { NL, KS[], NO[] }) and includes nf_mlp_split_table.h, which derives the rest from it.
 #pragma once
 #include "nf_common.h"
 
@@ -37,7 +37,8 @@ __host__ __device__ constexpr int pe_col(int s, int h, int j) {
 __host__ __device__ constexpr int dir_col(int h, int j) { return j < 4 ? 256 + 6 * (2 * h + (j >> 1)) + 3 * (j & 1) : -1; }
 }  // namespace nfb
 
-// A split forward kernel (nf_mlp_bf16_kernel.inc, nf_mlp_lcode_bf16_kernel.inc): 256 threads per 128 points; saved = NULL for the
+// A split forward kernel (a family's layer list in nf_mlp_bf16_kernel.inc / nf_mlp_lcode_bf16_kernel.inc around the text both share,
+// nf_mlp_split_fwd.inc): 256 threads per 128 points; saved = NULL for the
 // inference instantiations
 typedef void (*NfSplitFwdKernel)(const char* wstream, const float* cond, const float* ro, const float* rd, const float* rd_view,
                                  const float* z, int64_t n_points, int n_samples, float* raw, float* saved);
@@ -49,4 +50,23 @@ static inline int nf_split_fwd(NfSplitFwdKernel kernel, NfFwdMode mode, const vo
         hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, nf_s(stream), reinterpret_cast<const char*>(wstream), cond, ro, rd,
                            rd_view ? rd_view : rd, z, n_points, n_samples, raw, saved);
     });
+}
+
+// A split backward-chain kernel (a family's layer list in nf_mlp_bf16_bwd.hip / nf_mlp_lcode_bf16_bwd.hip around nf_mlp_split_bwd.inc),
+// same tiling; the unit is compiled once per arithmetic and NFB_BWD_NAME keeps the two sets of names apart.
+// gscale: 16 zeroed words on the device that receive max |dz| per layer (fp16 instantiation; ignored by the bf16 one)
+#if NFB_F16
+#define NFB_BWD_NAME(x) x##_f16
+#else
+#define NFB_BWD_NAME(x) x##_bf16
+#endif
+typedef void (*NfSplitBwdChainKernel)(const char* wstream, const float* saved, const float* d_raw, int64_t n_points, float* dz, float* gscale);
+
+static inline int nf_split_bwd_chain(NfSplitBwdChainKernel kernel, const void* packed_t, const float* saved, const float* d_raw,
+                                     int64_t n_points, float* dz, float* gscale, nf_stream_t stream) {
+    const int64_t grid = (n_points + 127) / 128;
+    if (grid > 0x7fffffff) return NF_EINVAL;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(256), 0, nf_s(stream), reinterpret_cast<const char*>(packed_t), saved, d_raw,
+                       n_points, dz, gscale);
+    NF_RETURN_LAUNCH();
 }
