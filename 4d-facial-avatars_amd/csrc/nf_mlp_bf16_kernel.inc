@@ -4,6 +4,11 @@
 // NFB_SAVE: training forward -- the layer outputs also go to `saved` (sections nfl::S_*) as the weight-gradient kernel's fragment
 // streams, plus the ReLU bit masks the split backward chain reads (nfl::S_MASK).
 // This file is the paper model's part: the bias-scaling list and the layer list; the rest of the body is nf_mlp_split_fwd.inc.
+// NFB_SIGMA_ONLY (with NFB_RUN_LAYERS 8, NFB_SAVE 0): the density-only inference kernels -- the list ends behind layers_dir.0, whose
+// tile 4 is fc_alpha, and `raw` receives one float per point.
+#ifndef NFB_SIGMA_ONLY
+#define NFB_SIGMA_ONLY 0
+#endif
 #include <type_traits>
 #include "nf_mlp_bf16_machinery.inc"
 
@@ -44,6 +49,10 @@ NFB_KERNEL_NAME(const char* __restrict__ wstream, const float* __restrict__ cond
         for (int j = 0; j < 8; ++j) { th[s][j] = (nfb_elt)0.f; tl[s][j] = (nfb_elt)0.f; }
     NFB_RUN(7, accB, th, tl, 8, accA, S_FEAT);
     const float sigma_raw = accB[4][0] * OUT_INV(7);
+#if NFB_SIGMA_ONLY
+    // density only (NFB_RUN_LAYERS = 8: the ring ends with this layer's last stage)
+    NFB_STORE_SIGMA();
+#else
     NFB_FINISH(7, accB, 4, true, nfb_mask_index(S_D0));
     // ---- layers_dir.1, .2 ----------------------------------------------------------------------------------------------
     nfb_init_bias<4>(accA, bias + B_D1, h);
@@ -62,4 +71,5 @@ NFB_KERNEL_NAME(const char* __restrict__ wstream, const float* __restrict__ cond
     for (int s = 0; s < 8; ++s) { th[s] = bh[4 + s]; tl[s] = bl[4 + s]; }
     NFB_RUN(10, accA, th, tl, 4, accB, S_D2);
     NFB_STORE_RAW(10, accA, B_RGB);
+#endif
 }

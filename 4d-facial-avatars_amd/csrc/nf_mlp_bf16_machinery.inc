@@ -25,7 +25,13 @@ namespace nfb {
 // global stage table (compile time): stage g -> (first stream block, number of blocks)
 constexpr int stages_of(int l) { return KS[l] / NFB_KPS; }
 constexpr int stage0_of(int l) { int o = 0; for (int i = 0; i < l; ++i) o += stages_of(i); return o; }
-constexpr int N_STAGES = stage0_of(NL);
+// NFB_RUN_LAYERS (density-only kernels): the kernel ends behind stream layer NFB_RUN_LAYERS - 1.  The ring then ends there too: a
+// stage past it has no blocks, so it is never issued (stage_nblk) and never waited for (inflight_after), and the last stage that
+// runs leaves with vmcnt(0) -- no DMA into LDS is outstanding at kernel exit.
+#ifndef NFB_RUN_LAYERS
+#define NFB_RUN_LAYERS NL
+#endif
+constexpr int N_STAGES = stage0_of(NFB_RUN_LAYERS);
 constexpr int layer_of_stage(int g) { int l = 0; while (l < NL && g >= stage0_of(l + 1)) ++l; return l; }
 constexpr int stage_nblk(int g) { return (g < 0 || g >= N_STAGES) ? 0 : 2 * NFB_KPS * NO[layer_of_stage(g)]; }
 // DMA pieces of this wave that may stay in flight when stage g ends: those of stages g+2 .. g+NFB_LA

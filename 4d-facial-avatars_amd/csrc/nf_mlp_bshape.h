@@ -180,6 +180,22 @@ __device__ __forceinline__ void nf_bs_bias_table(const float* __restrict__ packe
                                        const float* z, int64_t n_rays, int n_samples, float* raw, nf_stream_t stream) {                   \
         return nf_lcode_mlp_fwd_f16x2(packed, cond, ro, rd, rd_view, z, n_rays, n_samples, raw, stream);                                  \
     }                                                                                                                                     \
+    extern "C" int PFX##_mlp_sigma(const float* packed, const float* cond, const float* ro, const float* rd, const float* rd_view,        \
+                                   const float* z, int64_t n_rays, int n_samples, float* sigma, nf_stream_t stream) {                     \
+        return nf_lcode_mlp_sigma(packed, cond, ro, rd, rd_view, z, n_rays, n_samples, sigma, stream);                                    \
+    }                                                                                                                                     \
+    extern "C" int PFX##_mlp_sigma_bf16(const void* packed, const float* cond, const float* ro, const float* rd, const float* rd_view,    \
+                                        const float* z, int64_t n_rays, int n_samples, float* sigma, nf_stream_t stream) {                \
+        return nf_lcode_mlp_sigma_bf16(packed, cond, ro, rd, rd_view, z, n_rays, n_samples, sigma, stream);                               \
+    }                                                                                                                                     \
+    extern "C" int PFX##_mlp_sigma_f16(const void* packed, const float* cond, const float* ro, const float* rd, const float* rd_view,     \
+                                       const float* z, int64_t n_rays, int n_samples, float* sigma, nf_stream_t stream) {                 \
+        return nf_lcode_mlp_sigma_f16(packed, cond, ro, rd, rd_view, z, n_rays, n_samples, sigma, stream);                                \
+    }                                                                                                                                     \
+    extern "C" int PFX##_mlp_sigma_f16x2(const void* packed, const float* cond, const float* ro, const float* rd, const float* rd_view,   \
+                                         const float* z, int64_t n_rays, int n_samples, float* sigma, nf_stream_t stream) {               \
+        return nf_lcode_mlp_sigma_f16x2(packed, cond, ro, rd, rd_view, z, n_rays, n_samples, sigma, stream);                              \
+    }                                                                                                                                     \
     extern "C" size_t PFX##_saved_floats(int64_t n_points) { return nf_lcode_saved_floats(n_points); }                                    \
     extern "C" int PFX##_mlp_fwd_train(const float* packed, const float* cond, const float* ro, const float* rd, const float* rd_view,    \
                                        const float* z, int64_t n_rays, int n_samples, float* raw, float* saved, nf_stream_t stream) {     \

@@ -3,6 +3,11 @@
 // NFB_SAVE: training forward -- every layer output also goes to `saved` (sections nlc::S_*) plus the ReLU bit masks the
 // split-bf16 backward chain reads (nlc::S_MASK).
 // This file is the family's part: the bias-scaling list and the layer list; the rest of the body is nf_mlp_split_fwd.inc.
+// NFB_SIGMA_ONLY (with NFB_RUN_LAYERS 5, NFB_SAVE 0): the density-only inference kernels -- the list ends behind fc_alpha and `raw`
+// receives one float per point.
+#ifndef NFB_SIGMA_ONLY
+#define NFB_SIGMA_ONLY 0
+#endif
 #include <type_traits>
 #include "nf_mlp_bf16_machinery.inc"
 
@@ -37,6 +42,10 @@ NFB_KERNEL_NAME(const char* __restrict__ wstream, const float* __restrict__ cond
     if (h == 0) accA[0][0] = bias[B_ALPHA];
     NFB_LAYER(4, accA, th, tl);
     const float sigma_raw = accA[0][0] * OUT_INV(4);
+#if NFB_SIGMA_ONLY
+    // density only (NFB_RUN_LAYERS = 5: the ring ends with fc_alpha's last stage)
+    NFB_STORE_SIGMA();
+#else
     nfb_init_bias<8>(accA, bias + B_FEAT, h);
     NFB_RUN(5, accA, th, tl, 8, accB, S_X2);
     NFB_FINISH(5, accA, 8, true, 3);
@@ -57,4 +66,5 @@ NFB_KERNEL_NAME(const char* __restrict__ wstream, const float* __restrict__ cond
     for (int s = 0; s < 8; ++s) { th[s] = bh[4 + s]; tl[s] = bl[4 + s]; }
     NFB_RUN(7, accA, th, tl, 4, accB, S_DIR);
     NFB_STORE_RAW(7, accA, B_RGB);
+#endif
 }

@@ -294,7 +294,10 @@ __device__ __forceinline__ void nf_paper_net_store_raw(const f32x4 (&acc)[NT][16
 // weights and first B fragment fetched), every layer starts with the bias as the C operand of its first MFMAs, the ReLU is applied
 // where the slab is read.  NDIR register chunks of direction slots (1: (sin, cos)(rd_z 2^g), weights OFF_D0; 2: the 24 reference
 // columns, weights OFF_D0E) follow layers_dir.0's 16 feat chunks.  Leaves rgb_raw in acc[t][0].xyz and sigma_raw in sigma_raw[t].
-template <class Net, int NT, int NDIR>
+// SIGMA: the density-only forward.  Behind fc_feat only fc_alpha runs -- tile 8 of layers_dir.0 over its 16 feat chunks, the same
+// MFMAs in the same order as the full layer issues for acc[t][8]; the direction chunk, whose alpha row is zero, and everything
+// behind the layer are neither fetched nor issued.  Leaves sigma_raw[t]; acc[t][0] is not a colour.
+template <class Net, int NT, int NDIR, bool SIGMA = false>
 __device__ __forceinline__ void nf_paper_net_body(f32x4 (&acc)[NT][16], float (&sigma_raw)[NT], const f32x4 (&pe)[NT][4],
                                                   const f32x4 (&dirf)[NT][NDIR], const NfW& Wi, const NfW& Ci, f32x4* act4, int lane) {
     constexpr unsigned D0 = (NDIR == 1 ? Net::OFF_D0 : Net::OFF_D0E) / 4;
@@ -317,6 +320,30 @@ __device__ __forceinline__ void nf_paper_net_body(f32x4 (&acc)[NT][16], float (&
         NF_NET_LAYER256(Net::OFF_L4 / 4, true, Net::OFF_FEAT / 4, Net::B_FEAT, 16, 1);
     }
     // fc_feat (no activation: layers_dir.0 reads it as stored)
+    if constexpr (SIGMA) {
+        NF_NET_LAYER256(Net::OFF_FEAT / 4, true, D0 + 8 * 64, Net::B_D0 + 128, 1, 1);      // next: tile 8 alone, its bias fragment
+        f32x4 w8[16];
+        w8[0] = st.wa[0];
+#pragma unroll
+        for (int ch = 1; ch < 16; ++ch) w8[ch] = nf_load_w1(Wi, D0 + (9 * ch + 8) * 64, lane);
+#pragma unroll
+        for (int ch = 0; ch < 16; ++ch) {
+            if (ch == 0) {
+#pragma unroll
+                for (int t = 0; t < NT; ++t) bj[t] = st.b0[t];
+            } else {
+                nf_read_b<NT>(bj, act4, lane, ch);
+            }
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+#pragma unroll
+                for (int t = 0; t < NT; ++t)
+                    acc[t][8] = __builtin_amdgcn_mfma_f32_16x16x4f32(w8[ch][r], bj[t][r], (ch == 0 && r == 0) ? st.bias[0] : acc[t][8], 0, 0, 0);
+        }
+#pragma unroll
+        for (int t = 0; t < NT; ++t) sigma_raw[t] = acc[t][8].x;
+        return;
+    }
     NF_NET_LAYER256(Net::OFF_FEAT / 4, true, D0, Net::B_D0, 9, 1);
 #undef NF_NET_LAYER256
     // ---- layers_dir.0 : [feat | dir slots] -> 128; tile 8 row 0 = fc_alpha(feat) (Q2) -----------------------
@@ -530,5 +557,59 @@ static inline int nf_paper_net_launch_fwd(Fwd fwd, FwdSave fwd_save, const float
         else
             hipLaunchKernelGGL(fwd, dim3((unsigned)(grid < nf_cu_count() ? grid : nf_cu_count())), dim3(64 * NF_MLP_WAVES), 0, nf_s(stream),
                                packed, cond, ro, rd, rdv, z, n_points, n_samples, raw);
+    });
+}
+
+// Density-only inference forward of one workgroup (nf_paper_net_body<..., SIGMA>): the persistent block loop of the family's
+// k_*_mlp_fwd, one float per point written.  The direction never reaches fc_alpha, so no rd_view is read.
+template <class Net, int NT>
+__device__ __forceinline__ void nf_paper_net_fwd_sigma(f32x4* lds, const float* __restrict__ packed, const float* __restrict__ cond_,
+                                                       const float* __restrict__ ro, const float* __restrict__ rd, const float* __restrict__ z,
+                                                       int64_t n_points, int S, float* __restrict__ sigma) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int c = lane & 15;
+    f32x4* act4 = lds + wave * (16 * NT * 64);
+    typedef __attribute__((address_space(1))) float nf_gf32;
+    nf_gf32* sigma_v = (nf_gf32*)sigma;               // the output pointer and the grid stride live in VGPRs, as in k_paper_mlp_fwd
+    asm volatile("" : "+v"(sigma_v));
+    int stride_v = (int)gridDim.x;
+    asm volatile("" : "+v"(stride_v));
+    const float* z_v = z;                             // (and the depths' pointer: the last scalar pair the block loop could not keep)
+    asm volatile("" : "+v"(z_v));
+#pragma unroll 1
+    for (int64_t blk = blockIdx.x;; blk += __builtin_amdgcn_readfirstlane(stride_v)) {
+        const int64_t p0 = (blk * NF_MLP_WAVES + wave) * (16 * NT);
+        if (p0 >= n_points) break;                    // wave-uniform; no barriers anywhere below
+        int opaque0 = 0;                              // per-block opaque zero: the weight / bias loads must stay where the layers issue them
+        asm volatile("" : "+s"(opaque0));
+        const float* W = packed + opaque0;
+        const float* cond = cond_ + opaque0;
+        f32x4 pe[NT][4];
+        f32x4 dirf[NT][1];
+        nf_paper_net_inputs<NT>(pe, dirf, p0, n_points, S, lane, ro, rd, rd, z_v);
+        f32x4 acc[NT][16];
+        float sigma_raw[NT];
+        const NfW Wi = nf_w_image(W, Net::PACKED), Ci = nf_w_image(cond, Net::COND_FLOATS);
+        nf_paper_net_body<Net, NT, 1, true>(acc, sigma_raw, pe, dirf, Wi, Ci, act4, lane);
+        int lane_o = lane;
+        asm volatile("" : "+v"(lane_o));
+        if ((lane_o >> 4) == 0) {
+#pragma unroll
+            for (int t = 0; t < NT; ++t) {
+                const int64_t p = p0 + 16 * t + c;
+                if (p < n_points) sigma_v[p] = sigma_raw[t];
+            }
+        }
+    }
+}
+
+// Launch of a family's k_*_mlp_sigma<NF_MLP_NT> (a persistent grid, at most one workgroup per CU); checks as the full forward's
+template <class Sigma>
+static inline int nf_paper_net_launch_sigma(Sigma kernel, const float* packed, const float* cond, const float* ro, const float* rd,
+                                            const float* z, int64_t n_rays, int n_samples, float* sigma, nf_stream_t stream) {
+    static_assert(NF_MLP_WAVES * 16 * NF_MLP_NT == 128, "nf_mlp_fwd_launch sizes the grid for 128 points per workgroup");
+    return nf_mlp_fwd_launch(NF_FWD_INFER, packed, cond, ro, rd, z, sigma, nullptr, n_rays, n_samples, [&](int64_t n_points, unsigned grid) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)(grid < nf_cu_count() ? grid : nf_cu_count())), dim3(64 * NF_MLP_WAVES), 0, nf_s(stream),
+                           packed, cond, ro, rd, z, n_points, n_samples, sigma);
     });
 }

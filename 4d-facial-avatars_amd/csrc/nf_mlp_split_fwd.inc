@@ -186,6 +186,12 @@
 #else
 #define NFB_RANGE_GUARD() (void)0
 #endif
+// density-only kernels (NFB_SIGMA_ONLY, NFB_RUN_LAYERS): `raw` is sigma[n_points]; the layer list ends here
+#define NFB_STORE_SIGMA()                                                                                \
+    do {                                                                                                 \
+        if (h == 0 && p_raw < n_points) raw[p_raw] = sigma_raw;                                          \
+        NFB_RANGE_GUARD();                                                                               \
+    } while (0)
 #define NFB_STORE_RAW(L_, acc_, BIAS_)                                                                   \
     do {                                                                                                 \
         if (h == 0 && p_raw < n_points) {                                                                \

@@ -59,6 +59,12 @@ __device__ __forceinline__ void nf_load_w16(f32x4 (&w)[16], const NfW& W, unsign
         w[no] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(W.rsrc, lane * 16 + (no & 3) * 1024, (int)(off4 * 16u) + (no >> 2) * 4096, 0));
 }
 
+// one weight fragment (f32x4 index off4 + lane); the whole offset rides in the vector address: sixteen of these in a row (the
+// density-only tail of nf_paper_net_body) would otherwise hold sixteen scalar offsets at once
+__device__ __forceinline__ f32x4 nf_load_w1(const NfW& W, unsigned off4, int lane) {
+    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(W.rsrc, lane * 16 + (int)(off4 * 16u), 0, 0));
+}
+
 // bias fragments of a layer: floats [off + 16 no + 4 g, + 4) of the per-call bias table `cond`
 template <int NO>
 __device__ __forceinline__ void nf_load_bias(f32x4 (&bias)[16], const NfW& C, unsigned off, int lane) {

@@ -70,6 +70,64 @@ extern "C" int nf_volume_render_fwd(const float* raw, const float* z, const floa
     NF_RETURN_LAUNCH();
 }
 
+// K5 without the colours (the colour-free coarse pass): weights, disparity and acc of k_volume_render_fwd in NeRFace mode from the
+// densities alone -- 4 B/sample of sigma read instead of 16 B/sample of raw.  Same mapping, same scans, the same nf_* helpers in
+// the same order as nf_load_sample and the loop above, so the three outputs are bit-identical to the full kernel's.
+__global__ void __launch_bounds__(256) k_volume_weights_fwd(const float* __restrict__ sigma, const float* __restrict__ z,
+                                                            const float* __restrict__ rd, const float* __restrict__ noise,
+                                                            int64_t n_rays, int S, float* __restrict__ disp, float* __restrict__ acc,
+                                                            float* __restrict__ weights) {
+    const int lane = nf_lane();
+    const int64_t ray = (int64_t)blockIdx.x * NF_RAYS_PER_BLOCK + (threadIdx.x >> 6);
+    if (ray >= n_rays) return;
+    const float* s_row = sigma + ray * S;
+    const float* z_row = z + ray * S;
+    const float* noise_row = noise ? noise + ray * S : nullptr;
+    const float norm = nf_rd_norm(rd + ray * 3);
+    float carry = 1.0f;                        // running exclusive transmittance at the chunk start
+    float a_d = 0.f, a_w = 0.f;
+    for (int base = 0; base < S; base += 64) {
+        const int s = base + lane;
+        const bool on = s < S;
+        float alpha = 0.f, zz = 0.f;
+        if (on) {
+            const bool last = (s == S - 1);
+            const float d = last ? 1e10f : nf_sub(z_row[s + 1], z_row[s]);
+            const float dist = nf_mul(d, norm);
+            const float pre = noise_row ? nf_add(s_row[s], noise_row[s]) : s_row[s];
+            float sg = pre < 0.0f ? 0.0f : pre;                       // torch.relu: a NaN density stays NaN
+            if (last) sg = nf_add(sg, 1e-6f);                         // V:52-53
+            alpha = nf_sub(1.0f, expf(-nf_mul(sg, dist)));
+            zz = z_row[s];
+        }
+        const float b = on ? nf_add(nf_sub(1.0f, alpha), 1e-10f) : 1.0f;
+        const float incl = wave_scan_mul(b);
+        float excl = __shfl_up(incl, 1, 64);
+        if (lane == 0) excl = 1.0f;
+        const float T = nf_mul(carry, excl);
+        const float w = nf_mul(alpha, T);
+        if (on) weights[ray * S + s] = w;
+        a_d += w * zz; a_w += w;
+        carry = nf_mul(carry, __shfl(incl, 63, 64));
+    }
+    a_d = wave_sum(a_d); a_w = wave_sum(a_w);
+    if (lane == 0) {
+        acc[ray] = a_w;
+        disp[ray] = nf_div(1.0f, fmaxf(1e-10f, nf_div(a_d, a_w)));
+    }
+}
+
+extern "C" int nf_volume_weights_fwd(const float* sigma, const float* z, const float* rd, const float* noise, int64_t n_rays,
+                                     int n_samples, float* disp, float* acc, float* weights, nf_stream_t stream) {
+    if (n_rays == 0) return 0;                       // nothing to do (empty tensors have NULL data pointers)
+    if (!sigma || !z || !rd || !disp || !acc || !weights || n_rays < 0 || n_samples <= 0) return NF_EINVAL;
+    const int64_t grid = (n_rays + NF_RAYS_PER_BLOCK - 1) / NF_RAYS_PER_BLOCK;
+    if (grid > 0x7fffffff) return NF_EINVAL;
+    hipLaunchKernelGGL(k_volume_weights_fwd, dim3((unsigned)grid), dim3(256), 0, nf_s(stream), sigma, z, rd, noise, n_rays, n_samples,
+                       disp, acc, weights);
+    NF_RETURN_LAUNCH();
+}
+
 // tiny_nerf's render_volume_density (reference tiny_nerf.py:68-107): no background sample, no +1e-6, spacing not scaled by
 // |rd|; returns (rgb_map, depth_map, acc_map).  depth: (n_rays, n_samples).
 extern "C" int nf_render_volume_density(const float* raw, const float* depth, int64_t n_rays, int n_samples, float* rgb,

@@ -114,6 +114,9 @@ def _main(argv=None):
     ap.add_argument("--metrics", action="store_true",
                     help="also compute L1, PSNR and SSIM of every frame as written (its uint8 bytes) against its test image, on the device, "
                          "and write savedir/metrics.txt in the layout of the reference's nerf/metrics.py (without LPIPS)")
+    ap.add_argument("--coarse-density-only", action="store_true",
+                    help="colour-free coarse pass (options.nerf.validation.coarse_density_only): the coarse network is evaluated up to its "
+                         "density only -- the written frames are the fine image and do not change by a byte; needs a fine network")
     ap.add_argument("--backend", choices=["nccl", "gloo"], default=os.environ.get("NERFACE_DIST_BACKEND", "nccl"))
     ap.add_argument("--as-shipped", action="store_true",
                     help="render exactly what eval_transformed_rays.py renders as shipped (EV:420-446): ablate = 'view_dir' -- pose and "
@@ -155,6 +158,10 @@ def _main(argv=None):
     model_c.eval()
     if model_f is not None:
         model_f.eval()
+    if args.coarse_density_only:
+        if model_f is None or int(cfg.nerf.validation.num_fine) <= 0:
+            raise SystemExit("--coarse-density-only: this config has no fine network, the coarse colour is the image")
+        cfg.nerf.validation.coarse_density_only = True
     os.makedirs(args.savedir, exist_ok=True)
     if args.save_disparity_image:
         os.makedirs(os.path.join(args.savedir, "disparity"), exist_ok=True)

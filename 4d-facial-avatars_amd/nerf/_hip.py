@@ -183,6 +183,13 @@ _FAMILY_ENTRY_POINTS = {          # <prefix>_<name> of a family with every arith
 }
 for _prefix in ("nf_bshape", "nf_cbshape"):
     _PROTOTYPES.update({f"{_prefix}_{_name}": _sig for _name, _sig in _FAMILY_ENTRY_POINTS.items()})
+# density only: <prefix>_mlp_sigma* = <prefix>_mlp_fwd* with sigma (n_rays * n_samples floats) in place of raw; the smaller paper
+# model is exact f32 only
+_SIGMA_SIG = (C.c_int, [_P, _P, _P, _P, _P, _P, _L, _I, _P, _P])
+SIGMA_ENTRY_POINTS = tuple(f"{_prefix}_mlp_sigma{_suffix}" for _prefix in ("nf_paper", "nf_lcode", "nf_bshape", "nf_cbshape")
+                           for _suffix in ("", "_bf16", "_f16", "_f16x2")) + ("nf_smaller_mlp_sigma",)
+_PROTOTYPES.update({_name: _SIGMA_SIG for _name in SIGMA_ENTRY_POINTS})
+_PROTOTYPES["nf_volume_weights_fwd"] = (C.c_int, [_P, _P, _P, _P, _L, _I, _P, _P, _P, _P])
 for _prefix in ("nf_lcode", "nf_bshape", "nf_cbshape"):          # measurement hook (tools/time_blendshape.py)
     _PROTOTYPES[f"{_prefix}_mlp_bwd_stage_ms"] = (C.c_int, [_P, _P, _I, _P, _P, _P, _L, _I, _P, _Z, _P, _P, _P])
 # entry points that later ABI revisions add; absent symbols only fail when called

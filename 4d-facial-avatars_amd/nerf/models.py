@@ -53,6 +53,20 @@ class _FusedNeRFModel(torch.nn.Module):
         image = {"f32": hw.get, "bf16x3": hw.get_bf16, "f16x3": hw.get_f16, "f16x2": hw.get_f16}[prec]()
         return ops.mlp_fwd(fam, prec, image, cond, ro, rd, z, rd_view), None
 
+    def hip_sigma(self, ro, rd, z, expr, latent, near, far):
+        """Raw sigma (R, S) for the points ro + rd*z in the arithmetic of nerf.set_mlp_precision: hip_forward(..., need_grad=False)[0][..., 3]
+        bit for bit, from the kernel that ends with the layer that yields the density.  Inference only; same precision handling,
+        conditioning check and f16 guard as hip_forward's inference branch."""
+        ops.check_conditioning(expr, latent)
+        fam, hw, prec = self.FAMILY, self.hip_weights(), ops.get_mlp_precision()
+        fam.require_precision(prec)
+        packed = hw.get()
+        cond = ops.mlp_condition(fam, packed, expr, latent, near, far)
+        if prec in ops.F16_MODES:
+            ops.f16_guard(self, ro, rd, z, None, expr, latent, near, far, training=False)
+        image = {"f32": hw.get, "bf16x3": hw.get_bf16, "f16x3": hw.get_f16, "f16x2": hw.get_f16}[prec]()
+        return ops.mlp_sigma(fam, prec, image, cond, ro, rd, z)
+
     def hip_backward(self, state, z, d_raw):
         """d_raw -> ([gradients in hip_param_list() order, None where autograd gives the reference None], d_latent (32))."""
         packed, cond, saved, split = state
@@ -70,6 +84,35 @@ class _FusedNeRFModel(torch.nn.Module):
             raise NotImplementedError(f"{type(self).__name__}.forward has no autograd on the MI355X build: train through "
                                       "nerf.run_one_iter_of_nerf(...), or call forward under torch.no_grad()")
         return ops.mlp_forward_encoded(self.hip_weights(), x, expr, latent_code)
+
+
+def density(model, points, expr, latent_code=None):
+    """Raw density (N,) of a fused model at arbitrary points (N, 3) for one expression (and latent code): raw[..., 3], before the
+    ReLU, in the arithmetic of nerf.set_mlp_precision.  The density depends on neither a view direction nor near / far, so none is
+    asked for: the points go through model.hip_sigma as ray origins with a zero direction (ro + 0 * 0 is ro exactly).  Inference
+    only; tensors on a ROCm device.  latent_code=None is allowed exactly for the classes whose forward ignores it."""
+    if not isinstance(model, _FusedNeRFModel) or not model.fused_supported() or (latent_code is None and model.NEEDS_LATENT):
+        raise NotImplementedError("density() is built for the NeRFace geometry and needs expr and latent_code")
+    if not (torch.is_tensor(points) and points.is_cuda and torch.is_tensor(expr) and expr.is_cuda):
+        raise RuntimeError("nerf (MI355X build): tensors must live on a ROCm device (`device='cuda'`); there is no CPU path in this package")
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError("expected points of shape (N, 3)")
+    if latent_code is None:
+        latent_code = torch.zeros(32, dtype=torch.float32, device=points.device)
+    if torch.is_grad_enabled() and (points.requires_grad or latent_code.requires_grad or any(p.requires_grad for p in model.parameters())):
+        raise NotImplementedError(f"{type(model).__name__}.forward has no autograd on the MI355X build: train through "
+                                  "nerf.run_one_iter_of_nerf(...), or call forward under torch.no_grad()")
+    n = points.shape[0]
+    if n == 0:
+        return torch.empty((0,), dtype=torch.float32, device=points.device)
+    ro = ops._c(points.detach().to(torch.float32))
+    expr = ops._c(expr.detach().to(torch.float32)).reshape(-1)
+    latent = ops._c(latent_code.detach().to(torch.float32)).reshape(-1)
+    ops.bump_pack_epoch()              # as run_one_iter_of_nerf: a weight image never outlives one call (ops.MLPWeights)
+    sigma = model.hip_sigma(ro, torch.zeros_like(ro), torch.zeros((n, 1), dtype=torch.float32, device=ro.device), expr, latent, 0.0, 0.0)
+    if ops.get_mlp_precision() in ops.F16_MODES:
+        ops.check_f16_range(model)
+    return sigma.reshape(n)
 
 
 class ConditionalBlendshapePaperNeRFModel(_FusedNeRFModel):

@@ -395,6 +395,22 @@ def mlp_fwd(fam: MLPFamily, precision: str, packed, cond, ro, rd, z, rd_view=Non
     return raw
 
 
+_SIGMA_ENTRY = {"f32": "mlp_sigma", "bf16x3": "mlp_sigma_bf16", "f16x3": "mlp_sigma_f16", "f16x2": "mlp_sigma_f16x2"}
+
+
+def mlp_sigma(fam: MLPFamily, precision: str, image, cond, ro, rd, z) -> torch.Tensor:
+    """Density-only inference forward of `fam` in arithmetic `precision` -> raw sigma (n_rays, n_samples), bit for bit
+    mlp_fwd(...)[..., 3]: the same kernel up to and including the layer that yields the density, nothing after it.  `image` as for
+    mlp_fwd.  The direction does not reach the density, so there is no rd_view."""
+    dev = H.require_device(image if precision == "f32" else None, cond, ro, rd, z)
+    n_rays, n_samples = z.shape
+    sigma = torch.empty((n_rays, n_samples), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        fam.call(_SIGMA_ENTRY[precision], H.ptr(image), H.ptr(cond), H.ptr(ro), H.ptr(rd), 0, H.ptr(z), n_rays, n_samples, H.ptr(sigma),
+                 H.stream_ptr(dev))
+    return sigma
+
+
 def mlp_fwd_train(fam: MLPFamily, packed, cond, ro, rd, z, rd_view=None, packed_b=None, packed_h=None):
     """Training forward of `fam`: returns (raw, (saved,)) where `saved` holds every layer output for the backward.
     packed_b (split-bf16 stream) or packed_h (split-fp16 stream) given -> the forward runs on that split kernel and `saved`
@@ -641,6 +657,20 @@ def volume_render_fwd(raw, z, rd, noise=None, bg=None, white_background=False):
                                              1 if white_background else 0, H.ptr(rgb), H.ptr(disp), H.ptr(acc), H.ptr(w),
                                              H.stream_ptr(dev)), "nf_volume_render_fwd")
     return rgb, disp, acc, w
+
+
+def volume_weights_fwd(sigma, z, rd, noise=None):
+    """(disp, acc, weights) of volume_render_fwd from sigma (n_rays, n_samples) = raw[..., 3] alone, bit for bit: they depend on the
+    density, z, |rd| and the noise only."""
+    dev = H.require_device(sigma, z, rd, noise)
+    n_rays, n_samples = z.shape
+    disp = torch.empty((n_rays,), dtype=torch.float32, device=dev)
+    acc = torch.empty((n_rays,), dtype=torch.float32, device=dev)
+    w = torch.empty((n_rays, n_samples), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        H.check(H.lib().nf_volume_weights_fwd(H.ptr(sigma), H.ptr(z), H.ptr(rd), H.ptr(noise), n_rays, n_samples, H.ptr(disp), H.ptr(acc),
+                                              H.ptr(w), H.stream_ptr(dev)), "nf_volume_weights_fwd")
+    return disp, acc, w
 
 
 def volume_render_bwd(raw, z, rd, noise, bg, d_rgb, white_background=False):

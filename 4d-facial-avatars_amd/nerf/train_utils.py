@@ -80,8 +80,14 @@ class _RenderChunk(torch.autograd.Function):
 
         lat_d = latent.detach().reshape(-1).contiguous()
         z_c = ops.sample_coarse(n_rays, nc, near, far, dev, t_rand, lindisp=cfg["lindisp"])
-        raw_c, state_c = model_c.hip_forward(ro, rd, z_c, rd_view, expr, lat_d, near, far, need_grad)
-        rgb_c, disp_c, acc_c, w_c = ops.volume_render_fwd(raw_c, z_c, rd, noise_c, bg, white)
+        if cfg.get("coarse_density_only"):
+            # colour-free coarse pass (inference with a fine network): the coarse weights, disparity and acc depend on the density
+            # alone, and the coarse colour is returned as None
+            raw_c = state_c = rgb_c = None
+            disp_c, acc_c, w_c = ops.volume_weights_fwd(model_c.hip_sigma(ro, rd, z_c, expr, lat_d, near, far), z_c, rd, noise_c)
+        else:
+            raw_c, state_c = model_c.hip_forward(ro, rd, z_c, rd_view, expr, lat_d, near, far, need_grad)
+            rgb_c, disp_c, acc_c, w_c = ops.volume_render_fwd(raw_c, z_c, rd, noise_c, bg, white)
         outs = [rgb_c, disp_c, acc_c]
         ctx.has_fine = nf > 0 and model_f is not None
         if ctx.has_fine:
@@ -188,6 +194,12 @@ def _render_rays(ro, rd, rd_view, model_coarse, model_fine, options, mode, expre
     # sample counts no render kernel is built for are refused here: before a random number is drawn or a kernel launched (the forward
     # integrator takes any count, so without this a training step beyond the backward's limit would only fail inside backward())
     ops.check_sample_counts(nc, nf if has_fine else 0, need_grad)
+    # options.nerf.<mode>.coarse_density_only (default False; no reference config has the key): the coarse pass computes densities only
+    density_only = bool(getattr(m, "coarse_density_only", False))
+    if density_only and not has_fine:
+        raise ValueError("coarse_density_only needs a fine network (num_fine > 0 and a fine model): the coarse colour would be the image")
+    if density_only and need_grad:
+        raise ValueError("coarse_density_only is an inference option: call under torch.no_grad() (the density-only kernels have no backward)")
     # ---- random draws, in the reference's order and shapes (T:75, V:41-50, H:363-367) --------------
     t_rand = torch.rand((n_rays, nc), dtype=torch.float32, device=dev) if m.perturb else None
     noise_c = (torch.randn((n_rays, nc), dtype=torch.float32, device=dev) * noise_std) if noise_std > 0.0 else None
@@ -203,7 +215,8 @@ def _render_rays(ro, rd, rd_view, model_coarse, model_fine, options, mode, expre
     expr = expressions.to(device=dev, dtype=torch.float32).reshape(-1).contiguous()
     cfg = dict(model_coarse=model_coarse, model_fine=model_fine if has_fine else None, near=near, far=far, num_coarse=nc,
                lindisp=bool(m.lindisp),
-               num_fine=nf if has_fine else 0, white_background=bool(m.white_background), need_grad=need_grad)
+               num_fine=nf if has_fine else 0, white_background=bool(m.white_background), need_grad=need_grad,
+               coarse_density_only=density_only)
     lat = latent_code if latent_code.dtype == torch.float32 else latent_code.to(torch.float32)
     outs = _RenderChunk.apply(cfg, ro, rd, rd_view, bg, expr, lat, t_rand, noise_c, u, noise_f, len(params_c),
                               *params_c, *params_f)

@@ -582,6 +582,34 @@ int nf_train_loss_bg_bwd(const float* rgb_coarse, const float* rgb_fine, const f
 /* ---- K7: per-ray ascending sort -- replaces torch.sort(...)[0] at T:126 --------------------------- */
 int nf_sort_rows(const float* in, int64_t n_rows, int n_cols, float* out, nf_stream_t stream);
 
+/* ---- density only (ABI 5 still: these only add) -----------------------------------------------------------------------------
+ * <prefix>_mlp_sigma*: the inference forward <prefix>_mlp_fwd* up to and including the layer that yields the raw density, and
+ * nothing after it: sigma[n_rays * n_samples] = raw[..., 3] of the full forward (before the ReLU), the same operations in the same
+ * order.  Arguments, images, bias table, NF_EINVAL / zero-ray conventions, valid range and range guard as the full forward of the
+ * same arithmetic; rd_view is accepted and not read by the exact-f32 kernels (the direction never reaches fc_alpha).  The smaller
+ * paper model has the exact-f32 form only, like its forward.                                                                   */
+#define NF_DECLARE_MLP_SIGMA(PFX)                                                                                                   \
+    int PFX##_mlp_sigma(const float* packed, const float* cond, const float* ro, const float* rd, const float* rd_view,            \
+                        const float* z, int64_t n_rays, int n_samples, float* sigma, nf_stream_t stream);
+#define NF_DECLARE_MLP_SIGMA_SPLIT(PFX)                                                                                             \
+    int PFX##_mlp_sigma_bf16(const void* packed_bf16, const float* cond, const float* ro, const float* rd, const float* rd_view,   \
+                             const float* z, int64_t n_rays, int n_samples, float* sigma, nf_stream_t stream);                     \
+    int PFX##_mlp_sigma_f16(const void* packed_f16, const float* cond, const float* ro, const float* rd, const float* rd_view,     \
+                            const float* z, int64_t n_rays, int n_samples, float* sigma, nf_stream_t stream);                      \
+    int PFX##_mlp_sigma_f16x2(const void* packed_f16, const float* cond, const float* ro, const float* rd, const float* rd_view,   \
+                              const float* z, int64_t n_rays, int n_samples, float* sigma, nf_stream_t stream);
+NF_DECLARE_MLP_SIGMA(nf_paper) NF_DECLARE_MLP_SIGMA_SPLIT(nf_paper)       /* nf_paper_mlp_sigma, _sigma_bf16, _sigma_f16, _sigma_f16x2 */
+NF_DECLARE_MLP_SIGMA(nf_lcode) NF_DECLARE_MLP_SIGMA_SPLIT(nf_lcode)
+NF_DECLARE_MLP_SIGMA(nf_bshape) NF_DECLARE_MLP_SIGMA_SPLIT(nf_bshape)
+NF_DECLARE_MLP_SIGMA(nf_cbshape) NF_DECLARE_MLP_SIGMA_SPLIT(nf_cbshape)
+NF_DECLARE_MLP_SIGMA(nf_smaller)                                          /* exact f32 only */
+#undef NF_DECLARE_MLP_SIGMA
+#undef NF_DECLARE_MLP_SIGMA_SPLIT
+/* K5 without the colours: weights (R,S), disp (R) and acc (R) of nf_volume_render_fwd from sigma (R,S) = raw[..., 3] alone, bit for
+ * bit (they depend on the density, z, |rd| and the noise only; neither the colours nor the background prior enter alpha).        */
+int nf_volume_weights_fwd(const float* sigma, const float* z, const float* rd, const float* noise, int64_t n_rays, int n_samples,
+                          float* disp, float* acc, float* weights, nf_stream_t stream);
+
 /* ---- host-only self-tests (no device needed): consistency of the weight-gradient job tables -- every slab entry written
  * exactly once per slice, tile ids inside their bundle.  0 = consistent, negative = which check failed.                 */
 int nf_selftest_dw_tables_f32(void);
