@@ -84,7 +84,7 @@ k_paper_mlp_fwd(const float* __restrict__ packed, const float* __restrict__ cond
 
     f32x4 pe[NT][4];
     f32x4 dirf[NT][1];
-    nf_paper_net_inputs<NT>(pe, dirf, p0, n_points, S, lane, ro, rd, rd_view, z);
+    nf_net_inputs<NT>(pe, dirf, p0, n_points, S, lane, ro, rd, rd_view, z);
     f32x4 acc[NT][16];
     float sigma_raw[NT];
     const NfW Wi = nf_w_image(reinterpret_cast<const float*>(W), PACKED_FLOATS), Ci = nf_w_image(cond, COND_FLOATS);

@@ -1,14 +1,11 @@
 // The two blendshape classes without a learnable code (reference nerf/models.py: ConditionalBlendshapeNeRFModel M:872-976,
 // ConditionalCompressedBlendshapeNeRFModel M:750-868) run on the second family's per-point kernels: per point they ARE that
 // network.  What differs is constant per call -- the vector folded into layer1's bias -- so each class owns its gather tables
-// (built by the second family's builders for its geometry), its condition kernel and its gradient scatter; everything per
-// point is launched through the nf_lcode_* entry points on images laid out as nf_mlp_lcode_layout.h says.
+// (built by the second family's builders for its geometry), its condition kernel and its gradient scatter -- both wrappers of the
+// family's trunk (nf_mlp_lcode_net.h, nf_mlp_lcode_net_bwd.h); everything per point is launched through the nf_lcode_* entry points
+// on images laid out as nf_mlp_lcode_layout.h says.
 #pragma once
-#include <vector>
-#include "nf_mlp_lcode_layout.h"
-#include "nf_mlp_bwd.h"
-#include "nf_pack.h"
-#include "../../include/nerface_hip.h"
+#include "nf_mlp_lcode_net_bwd.h"
 
 // ---- the compressed class: tail of its packed f32 image (the expression encoder, row-major) and its corner of `cond` ----
 namespace ncb {
@@ -31,99 +28,6 @@ constexpr int N_EXPR = 76;
 constexpr int LD1 = 63 + N_EXPR;
 constexpr int GRAD_PARAM_FLOATS = nlc::GRAD_PARAM_FLOATS - 256 * (171 - LD1);
 }  // namespace nbs
-
-// ---- what the second family's translation units provide -----------------------------------------------------------------
-void nf_lcode_build_table(std::vector<uint32_t>& t, const NfLcodeGeom& ge);           // exact-f32 image (nf_mlp_lcode.hip)
-void nf_lcode_build_table_t(std::vector<uint32_t>& t, const NfLcodeGeom& ge);         // transposed image (nf_mlp_lcode_bwd.hip)
-void nf_lcode_build_table_bf16(std::vector<uint32_t>& t, const NfLcodeGeom& ge);      // (hi, lo) stream (nf_mlp_lcode_bf16.hip)
-void nf_lcode_build_table_bf16_t(std::vector<uint32_t>& t, const NfLcodeGeom& ge);    // transposed stream (nf_mlp_lcode_bf16_bwd.hip)
-float nf_lcode_f16_stream_layers(int* pair_off);                                      // 8 + 1 offsets; returns the activation pre-scale
-void nf_lcode_bwd_f16_stream_layers(int* pair_off);                                   // 6 + 1 offsets
-int nf_lcode_launch_fwd_encoded(const float* packed, const float* cond, const float* x87, int64_t n_points, float* out, nf_stream_t stream);
-void nf_lcode_grad_reduce(const float* slabs, int ns, const NfReduceAlt& alt, float* sum, hipStream_t s);
-NfBwdFamily nf_lcode_bwd_family(void (*reduce_unpack)(const float*, int, const NfReduceAlt&, float*, const float*, const float*, float*,
-                                                      hipStream_t));
-
-// One trunk element of the flat gradient vector (the 16 tensors of nerf.ops.LCODE_KEYS order, layer1.weight LD1 columns wide) from the
-// reduced slab: k_lcode_grad_unpack's scatter with the class's column count; cvec = the folded vector (cond + B_CVEC).
-template <int LD1>
-struct NfBsGradOffsets { int off[nlc::NPARAMS + 1]; };
-
-template <int LD1>
-static inline NfBsGradOffsets<LD1> nf_bs_grad_offsets() {
-    const int numel[nlc::NPARAMS] = {256 * LD1, 256, 65536, 256, 65536, 256, 65536, 256, 128 * 280, 128, 256, 1, 384, 3, 65536, 256};
-    NfBsGradOffsets<LD1> o;
-    o.off[0] = 0;
-    for (int i = 0; i < nlc::NPARAMS; ++i) o.off[i + 1] = o.off[i] + numel[i];
-    return o;
-}
-
-template <int LD1>
-__device__ __forceinline__ float nf_bs_trunk_grad(int e, const NfBsGradOffsets<LD1>& offs, const float* __restrict__ sum,
-                                                  const float* __restrict__ cvec, const float* __restrict__ dvec) {
-    using namespace nlc;
-    int t = 0;
-    while (e >= offs.off[t + 1]) ++t;
-    const int local = e - offs.off[t];
-    switch (t) {
-        case 0: {  // layer1.weight [256][LD1] = [pe 63 | folded vector]
-            const int n = local / LD1, col = local - LD1 * n;
-            return col < 63 ? sum[G_L1 + n * 64 + nfl::pe_col_to_slot(col)] : sum[CS_L1 + n] * cvec[col - 63];
-        }
-        case 1: return sum[CS_L1 + local];
-        case 2: return sum[G_X0 + local];
-        case 3: return sum[CS_L1 + 256 + local];
-        case 4: return sum[G_X1 + local];
-        case 5: return sum[CS_L1 + 512 + local];
-        case 6: return sum[G_X2 + local];
-        case 7: return sum[CS_L1 + 768 + local];
-        case 8: {  // layers_dir.0.weight [128][280] = [feat 256 | PE4(rd_z, near, far) 24]
-            const int n = local / 280, col = local - 280 * n;
-            if (col < 256) return sum[G_DIRA + n * 256 + col];
-            const int q = col - 256, f = q / 6, rem = q - 6 * f, sc = rem / 3, comp = rem - 3 * sc;
-            return comp == 0 ? sum[G_DIRB + n * 16 + 4 * f + sc] : sum[CS_DIR + n] * dvec[4 * f + 2 * sc + (comp - 1)];
-        }
-        case 9: return sum[CS_DIR + local];
-        case 10: return sum[G_ALPHA + 3 * 256 + local];      // fc_alpha.weight [1][256] = row 3 (d sigma) of d_raw^T x
-        case 11: return sum[CS_RGB + 3];
-        case 12: return sum[G_RGB + local];                  // fc_rgb.weight [3][128]
-        case 13: return sum[CS_RGB + local];
-        case 14: return sum[G_FEAT + local];
-        default: return sum[CS_L1 + 1024 + local];
-    }
-}
-
-// the (near, far) direction features both classes fold into layers_dir.0's bias, as k_lcode_condition forms them
-__device__ __forceinline__ float nf_bs_dvec(int k, float near_z, float far_z) {
-    const int f = k >> 2, sc = (k >> 1) & 1, comp = k & 1;
-    const float a = nf_mul(comp ? far_z : near_z, exp2f((float)f));
-    return sc ? cosf(a) : sinf(a);
-}
-
-// The bias table from the folded vector cvec[108] (LDS; entries past N_COND are zero) and dvec[16]: k_lcode_condition's loop with the
-// class's column count, same fmaf order.  ENCODED: the table of <prefix>_forward_encoded (no direction fold, dvec = 0).
-template <int N_COND, bool ENCODED>
-__device__ __forceinline__ void nf_bs_bias_table(const float* __restrict__ packed, const float* cvec, const float* dvec,
-                                                 float* __restrict__ cond) {
-    using namespace nlc;
-    const float* bias = packed + OFF_BIAS;
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < COND_FLOATS; i += gridDim.x * blockDim.x) {
-        if (i >= B_CVEC) { cond[i] = i < B_DVEC ? cvec[i - B_CVEC] : (ENCODED ? 0.0f : dvec[i - B_DVEC]); continue; }
-        float v = bias[i];
-        if (i < B_X0) {
-            const float* w = packed + OFF_WC1 + i * 108;
-            float s = 0.0f;
-            for (int k = 0; k < N_COND; ++k) s = fmaf(w[k], cvec[k], s);
-            v += s;
-        } else if (!ENCODED && i >= B_DIR && i < B_DIR + 128) {
-            const float* w = packed + OFF_WCD + (i - B_DIR) * 16;
-            float s = 0.0f;
-            for (int k = 0; k < 16; ++k) s = fmaf(w[k], dvec[k], s);
-            v += s;
-        }
-        cond[i] = v;
-    }
-}
 
 // Every entry point of a class that is the second family's on the class's own images, and the six pack entry points.
 // PFX: nf_bshape / nf_cbshape; GEOM: the class's NfLcodeGeom; NP: its parameter count; TAG: keeps the pack kernels' instantiations

@@ -16,9 +16,9 @@ __global__ void __launch_bounds__(256) k_bshape_condition(const float* __restric
     __shared__ float dvec[16];
     const int tid = threadIdx.x;
     if (tid < 108) cvec[tid] = tid < nbs::N_EXPR ? nf_div(nf_mul(expr[tid], 1.0f), 3.0f) : 0.0f;
-    if (!ENCODED && tid >= 128 && tid < 144) dvec[tid - 128] = nf_bs_dvec(tid - 128, near_z, far_z);
+    if (!ENCODED && tid >= 128 && tid < 144) dvec[tid - 128] = nf_lcode_dvec(tid - 128, near_z, far_z);
     __syncthreads();
-    nf_bs_bias_table<nbs::N_EXPR, ENCODED>(packed, cvec, dvec, cond);
+    nf_lcode_bias_table<nbs::N_EXPR, ENCODED>(packed, cvec, dvec, cond);
 }
 
 extern "C" int nf_bshape_condition(const float* packed, const float* expr76, const float* latent32, float near_z, float far_z,
@@ -42,13 +42,13 @@ extern "C" int nf_bshape_forward_encoded(const float* packed, const float* x87, 
 
 // k_lcode_grad_unpack with 139 columns; the last workgroup writes the 32 zeros of d latent
 __global__ void __launch_bounds__(256) k_bshape_grad_unpack(const float* __restrict__ sum, const float* __restrict__ cond,
-                                                            NfBsGradOffsets<nbs::LD1> offs, float* __restrict__ grads) {
+                                                            NfLcodeGradOffsets<nbs::LD1> offs, float* __restrict__ grads) {
     if (blockIdx.x == gridDim.x - 1) {
         if (threadIdx.x < 32) grads[nbs::GRAD_PARAM_FLOATS + threadIdx.x] = 0.0f;
         return;
     }
     for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < nbs::GRAD_PARAM_FLOATS; e += (gridDim.x - 1) * blockDim.x)
-        grads[e] = nf_bs_trunk_grad<nbs::LD1>(e, offs, sum, cond + nlc::B_CVEC, cond + nlc::B_DVEC);
+        grads[e] = nf_lcode_trunk_grad<nbs::LD1>(e, offs, sum, cond + nlc::B_CVEC, cond + nlc::B_DVEC);
 }
 
 extern "C" size_t nf_bshape_grad_floats(void) { return (size_t)nbs::GRAD_PARAM_FLOATS + 32; }
@@ -58,7 +58,7 @@ static void nf_bshape_reduce_unpack(const float* slabs, int ns, const NfReduceAl
                                     float* grads, hipStream_t s) {
     (void)packed;
     nf_lcode_grad_reduce(slabs, ns, alt, sum, s);
-    hipLaunchKernelGGL(k_bshape_grad_unpack, dim3(1024 + 1), dim3(256), 0, s, sum, cond, nf_bs_grad_offsets<nbs::LD1>(), grads);
+    hipLaunchKernelGGL(k_bshape_grad_unpack, dim3(1024 + 1), dim3(256), 0, s, sum, cond, nf_lcode_grad_offsets<nbs::LD1>(), grads);
 }
 
 NF_BSHAPE_SHARED_ENTRY_POINTS(nf_bshape, NF_BSHAPE_GEOM, 16, 40, nf_bshape_table, nlc::PACKED)

@@ -43,7 +43,7 @@ __global__ void __launch_bounds__(256) k_cbshape_condition(const float* __restri
     const float* enc = packed + OFF_ENC;
     if (tid < D0) x0[tid] = expr[tid];
     if (tid < 108) cvec[tid] = 0.0f;
-    if (!ENCODED && tid >= 128 && tid < 144) dvec[tid - 128] = nf_bs_dvec(tid - 128, near_z, far_z);
+    if (!ENCODED && tid >= 128 && tid < 144) dvec[tid - 128] = nf_lcode_dvec(tid - 128, near_z, far_z);
     __syncthreads();
     nf_cb_enc_layer<D1, D0>(enc + E_W0, enc + E_B0, x0, e1);
     nf_cb_enc_layer<D2, D1>(enc + E_W1, enc + E_B1, e1, e2);
@@ -54,7 +54,7 @@ __global__ void __launch_bounds__(256) k_cbshape_condition(const float* __restri
         if (tid < D2) cond[C_E2 + tid] = e2[tid];
         if (tid < D3) cond[C_E3 + tid] = cvec[tid];
     }
-    nf_bs_bias_table<D3, ENCODED>(packed, cvec, dvec, cond);
+    nf_lcode_bias_table<D3, ENCODED>(packed, cvec, dvec, cond);
 }
 
 extern "C" int nf_cbshape_condition(const float* packed, const float* expr76, const float* latent32, float near_z, float far_z,
@@ -102,34 +102,17 @@ __device__ __forceinline__ void nf_cb_enc_layer_bwd(const float* __restrict__ w,
 // The 16 trunk tensors with 83 columns (d layer1.weight[n][63 + k] = cs_L1[n] e3[k]: B_CVEC holds e3); the last workgroup does the
 // encoder's backward -- fixed summation order, no atomics -- and writes the 32 zeros of d latent.
 __global__ void __launch_bounds__(256) k_cbshape_grad_unpack(const float* __restrict__ sum, const float* __restrict__ packed,
-                                                             const float* __restrict__ cond, NfBsGradOffsets<ncb::LD1> offs,
+                                                             const float* __restrict__ cond, NfLcodeGradOffsets<ncb::LD1> offs,
                                                              float* __restrict__ grads) {
     using namespace ncb;
     if (blockIdx.x == gridDim.x - 1) {
-        __shared__ float part[8][32];
         __shared__ float x0[D0], e1[D1], e2[D2], e3[D3], d1[D1], d2[D2], d3[D3];
         const int tid = threadIdx.x;
         if (tid < D0) x0[tid] = cond[C_EXPR + tid];
         if (tid < D1) e1[tid] = cond[C_E1 + tid];
         if (tid < D2) e2[tid] = cond[C_E2 + tid];
         if (tid < D3) e3[tid] = cond[C_E3 + tid];
-        // d e3[k] = sum_n layer1.weight[n][63 + k] d b1[n]: thread (q, k) sums n = 32 q .. 32 q + 31, the eight partial sums are added in
-        // a fixed order (the form of k_lcode_grad_unpack's d-latent workgroup)
-        const int k = tid & 31, q = tid >> 5;
-        float v = 0.0f;
-        if (k < D3) {
-            const float* w1 = packed + nlc::OFF_WC1 + k;
-#pragma unroll 8
-            for (int n = 32 * q; n < 32 * q + 32; ++n) v += w1[n * 108] * sum[nlc::CS_L1 + n];
-        }
-        part[q][k] = v;
-        __syncthreads();
-        if (tid < D3) {
-            float r = part[0][tid];
-#pragma unroll
-            for (int j = 1; j < 8; ++j) r += part[j][tid];
-            d3[tid] = r;
-        }
+        nf_lcode_dcond(packed, sum, 0, D3, d3);               // d e3[k] = sum_n layer1.weight[n][63 + k] d b1[n]
         __syncthreads();
         const float* enc = packed + OFF_ENC;
         nf_cb_enc_layer_bwd<D3, D2, true>(enc + E_W2, e3, e2, d3, d2, grads + E_W2, grads + E_B2);
@@ -139,7 +122,7 @@ __global__ void __launch_bounds__(256) k_cbshape_grad_unpack(const float* __rest
         return;
     }
     for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < GRAD_PARAM_FLOATS - ENC_FLOATS; e += (gridDim.x - 1) * blockDim.x)
-        grads[ENC_FLOATS + e] = nf_bs_trunk_grad<LD1>(e, offs, sum, cond + nlc::B_CVEC, cond + nlc::B_DVEC);
+        grads[ENC_FLOATS + e] = nf_lcode_trunk_grad<LD1>(e, offs, sum, cond + nlc::B_CVEC, cond + nlc::B_DVEC);
 }
 
 extern "C" size_t nf_cbshape_grad_floats(void) { return (size_t)ncb::GRAD_PARAM_FLOATS + 32; }
@@ -148,7 +131,7 @@ extern "C" size_t nf_cbshape_grad_floats(void) { return (size_t)ncb::GRAD_PARAM_
 static void nf_cbshape_reduce_unpack(const float* slabs, int ns, const NfReduceAlt& alt, float* sum, const float* packed, const float* cond,
                                      float* grads, hipStream_t s) {
     nf_lcode_grad_reduce(slabs, ns, alt, sum, s);
-    hipLaunchKernelGGL(k_cbshape_grad_unpack, dim3(1024 + 1), dim3(256), 0, s, sum, packed, cond, nf_bs_grad_offsets<ncb::LD1>(), grads);
+    hipLaunchKernelGGL(k_cbshape_grad_unpack, dim3(1024 + 1), dim3(256), 0, s, sum, packed, cond, nf_lcode_grad_offsets<ncb::LD1>(), grads);
 }
 
 NF_BSHAPE_SHARED_ENTRY_POINTS(nf_cbshape, NF_CBSHAPE_GEOM, ncb::NPARAMS, 50, nf_cbshape_table, ncb::PACKED)

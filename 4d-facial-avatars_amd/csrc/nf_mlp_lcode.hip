@@ -6,13 +6,7 @@
 // Inference forward, exact-f32 MFMA, same building blocks / folding rules as the paper model (nf_mlp.hip).
 #include <vector>
 #include <mutex>
-#include "nf_mlp_dev.h"
-#include "nf_mlp_stream.h"
-
-#include "nf_mlp_lcode_layout.h"
-#include "nf_pack.h"
-
-
+#include "nf_mlp_lcode_net.h"
 
 // gather table of the exact-f32 image for a class of geometry `ge` (nf_mlp_lcode_layout.h)
 void nf_lcode_build_table(std::vector<uint32_t>& t, const NfLcodeGeom& ge) {
@@ -68,35 +62,14 @@ extern "C" int nf_lcode_pack(const float* const* params, float* packed, nf_strea
 __global__ void __launch_bounds__(256) k_lcode_condition(const float* __restrict__ packed, const float* __restrict__ expr,
                                                          const float* __restrict__ latent, float near_z, float far_z,
                                                          float* __restrict__ cond) {
-    using namespace nlc;
     __shared__ float cvec[108];
     __shared__ float dvec[16];
     const int tid = threadIdx.x;
-    if (tid < 76) cvec[tid] = nf_div(nf_mul(expr[tid], 1.0f), 3.0f);
+    if (tid < 76) cvec[tid] = nf_div(nf_mul(expr[tid], 1.0f), 3.0f);        // (expr * 1) / 3, a true division
     else if (tid < 108) cvec[tid] = latent[tid - 76];
-    if (tid >= 128 && tid < 144) {
-        const int k = tid - 128, f = k >> 2, sc = (k >> 1) & 1, comp = k & 1;
-        const float a = nf_mul(comp ? far_z : near_z, exp2f((float)f));
-        dvec[k] = sc ? cosf(a) : sinf(a);
-    }
+    if (tid >= 128 && tid < 144) dvec[tid - 128] = nf_lcode_dvec(tid - 128, near_z, far_z);
     __syncthreads();
-    const float* bias = packed + OFF_BIAS;
-    for (int i = blockIdx.x * blockDim.x + tid; i < COND_FLOATS; i += gridDim.x * blockDim.x) {
-        if (i >= B_CVEC) { cond[i] = i < B_DVEC ? cvec[i - B_CVEC] : dvec[i - B_DVEC]; continue; }
-        float v = bias[i];
-        if (i < B_X0) {
-            const float* w = packed + OFF_WC1 + i * 108;
-            float s = 0.0f;
-            for (int k = 0; k < 108; ++k) s = fmaf(w[k], cvec[k], s);
-            v += s;
-        } else if (i >= B_DIR && i < B_DIR + 128) {
-            const float* w = packed + OFF_WCD + (i - B_DIR) * 16;
-            float s = 0.0f;
-            for (int k = 0; k < 16; ++k) s = fmaf(w[k], dvec[k], s);
-            v += s;
-        }
-        cond[i] = v;
-    }
+    nf_lcode_bias_table<108, false>(packed, cvec, dvec, cond);
 }
 
 extern "C" int nf_lcode_condition(const float* packed, const float* expr76, const float* latent32, float near_z, float far_z,
@@ -113,9 +86,18 @@ k_lcode_mlp_fwd(const float* __restrict__ packed, const float* __restrict__ cond
                 const float* __restrict__ rd, const float* __restrict__ rd_view, const float* __restrict__ z, int64_t n_points, int S,
                 float* __restrict__ raw) {
     __shared__ __attribute__((aligned(16))) f32x4 lds[NF_MLP_WAVES * 16 * NT * 64];
-#define NF_LCODE_SIGMA_ONLY 0
-#include "nf_mlp_lcode_fwd.inc"
-#undef NF_LCODE_SIGMA_ONLY
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t p0 = ((int64_t)blockIdx.x * NF_MLP_WAVES + wave) * (16 * NT);
+    if (p0 >= n_points) return;                       // wave-uniform; no barriers anywhere below
+    f32x4* act4 = lds + wave * (16 * NT * 64);
+    f32x4 pe[NT][4];
+    f32x4 dirf[NT][1];
+    nf_net_inputs<NT>(pe, dirf, p0, n_points, S, lane, ro, rd, rd_view, z);
+    f32x4 acc[NT][16];
+    float sigma_raw[NT];
+    const NfW Wi = nf_w_image(packed, nlc::PACKED), Ci = nf_w_image(cond, nlc::COND_FLOATS);
+    nf_lcode_net_body<NT, 1>(acc, sigma_raw, pe, dirf, Wi, Ci, act4, lane);
+    nf_net_store_raw<NT>(acc, sigma_raw, p0, n_points, lane, raw);
 }
 
 // ConditionalBlendshapeLearnableCodeNeRFModel.forward on PRE-ENCODED inputs (reference nerf/models.py:590-636 as called by run_network,
@@ -124,128 +106,32 @@ k_lcode_mlp_fwd(const float* __restrict__ packed, const float* __restrict__ cond
 // with its 24 direction columns as two register chunks (weights OFF_DIRE), bias table without the direction fold.
 __global__ void __launch_bounds__(256) k_lcode_condition_encoded(const float* __restrict__ packed, const float* __restrict__ expr,
                                                                  const float* __restrict__ latent, float* __restrict__ cond) {
-    using namespace nlc;
     __shared__ float cvec[108];
     const int tid = threadIdx.x;
     if (tid < 76) cvec[tid] = nf_div(nf_mul(expr[tid], 1.0f), 3.0f);
     else if (tid < 108) cvec[tid] = latent[tid - 76];
     __syncthreads();
-    const float* bias = packed + OFF_BIAS;
-    for (int i = blockIdx.x * blockDim.x + tid; i < COND_FLOATS; i += gridDim.x * blockDim.x) {
-        if (i >= B_CVEC) { cond[i] = i < B_DVEC ? cvec[i - B_CVEC] : 0.0f; continue; }
-        float v = bias[i];
-        if (i < B_X0) {
-            const float* w = packed + OFF_WC1 + i * 108;
-            float s = 0.0f;
-            for (int k = 0; k < 108; ++k) s = fmaf(w[k], cvec[k], s);
-            v += s;
-        }
-        cond[i] = v;
-    }
+    nf_lcode_bias_table<108, true>(packed, cvec, nullptr, cond);
 }
 
 template <int NT>
 __global__ void __launch_bounds__(64 * NF_MLP_WAVES, 1)
 k_lcode_mlp_fwd_encoded(const float* __restrict__ packed, const float* __restrict__ cond, const float* __restrict__ x87, int64_t n_points,
                         float* __restrict__ out) {
-    using namespace nlc;
     __shared__ __attribute__((aligned(16))) f32x4 lds[NF_MLP_WAVES * 16 * NT * 64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int g = lane >> 4, c = lane & 15;
     const int64_t p0 = ((int64_t)blockIdx.x * NF_MLP_WAVES + wave) * (16 * NT);
     if (p0 >= n_points) return;
     f32x4* act4 = lds + wave * (16 * NT * 64);
     f32x4 pe[NT][4];
     f32x4 dirf[NT][2];
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-        int64_t p = p0 + 16 * t + c;
-        if (p >= n_points) p = n_points - 1;
-        const float* row = x87 + p * 87;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            float v[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int col = nfl::pe_slot_to_col(16 * j + 4 * g + r);
-                v[r] = col >= 0 ? row[col] : 0.0f;
-            }
-            pe[t][j] = (f32x4){v[0], v[1], v[2], v[3]};
-        }
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            float v[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int s = 16 * j + 4 * g + r;
-                v[r] = s < 24 ? row[63 + s] : 0.0f;
-            }
-            dirf[t][j] = (f32x4){v[0], v[1], v[2], v[3]};
-        }
-    }
+    nf_net_inputs_encoded<NT>(pe, dirf, p0, n_points, lane, x87);
     f32x4 acc[NT][16];
-    NfStream<NT> st;
-    f32x4 bj[NT];
     float sigma_raw[NT];
-    const NfW Wi = nf_w_image(packed, PACKED), Ci = nf_w_image(cond, COND_FLOATS);
-#define NF_PE_B(J_) do { _Pragma("unroll") for (int t = 0; t < NT; ++t) bj[t] = pe[t][J_]; } while (0)
-    nf_load_bias<16>(st.bias, Ci, B_L1, lane);                           // layer1: no activation (M:609)
-    {
-        f32x4 w[16];
-        nf_load_w16<16>(w, Wi, OFF_L1 / 4, lane);
-        NF_PE_B(0); nf_chunk<NT, 16, true>(acc, w, bj, st.bias);
-        nf_load_w16<16>(w, Wi, OFF_L1 / 4 + 1 * 16 * 64, lane);
-        NF_PE_B(1); nf_chunk<NT, 16, false>(acc, w, bj, st.bias);
-        nf_load_w16<16>(w, Wi, OFF_L1 / 4 + 2 * 16 * 64, lane);
-        NF_PE_B(2); nf_chunk<NT, 16, false>(acc, w, bj, st.bias);
-        nf_load_w16<16>(w, Wi, OFF_L1 / 4 + 3 * 16 * 64, lane);
-        NF_PE_B(3); nf_tail<NT, 16, 16, 16, 1>(acc, w, bj, st, Wi, OFF_X0 / 4, Ci, B_X0, act4, lane);
-    }
-#undef NF_PE_B
-    nf_seg_lds<NT, 16, true, false>(acc, st, Wi, OFF_X0 / 4, 16, act4, lane);       // reads layer1's output as stored
-    nf_pending_b<NT, false>(bj, st);
-    nf_tail<NT, 16, 16, 16, 1>(acc, st.wb, bj, st, Wi, OFF_X1 / 4, Ci, B_X1, act4, lane);
-    nf_seg_lds<NT, 16, true, true>(acc, st, Wi, OFF_X1 / 4, 16, act4, lane);
-    nf_pending_b<NT, true>(bj, st);
-    nf_tail<NT, 16, 16, 16, 1>(acc, st.wb, bj, st, Wi, OFF_X2 / 4, Ci, B_X2, act4, lane);
-    nf_seg_lds<NT, 16, true, true>(acc, st, Wi, OFF_X2 / 4, 16, act4, lane);
-    nf_pending_b<NT, true>(bj, st);
-    nf_tail<NT, 16, 16, 1, 1>(acc, st.wb, bj, st, Wi, OFF_ALPHA / 4, Ci, B_ALPHA, act4, lane);
-    nf_seg_lds<NT, 1, true, true>(acc, st, Wi, OFF_ALPHA / 4, 16, act4, lane);      // fc_alpha(x)
-    nf_pending_b<NT, true>(bj, st);
-    nf_tail<NT, 1, 0, 16, 1>(acc, st.wb, bj, st, Wi, OFF_FEAT / 4, Ci, B_FEAT, act4, lane);
-#pragma unroll
-    for (int t = 0; t < NT; ++t) sigma_raw[t] = acc[t][0].x;
-    nf_seg_lds<NT, 16, true, true>(acc, st, Wi, OFF_FEAT / 4, 16, act4, lane);      // feat = relu(fc_feat(x)): the ReLU is the reader's
-    nf_pending_b<NT, true>(bj, st);
-    nf_tail<NT, 16, 16, 8, 1>(acc, st.wb, bj, st, Wi, OFF_DIRE / 4, Ci, B_DIR, act4, lane);
-    {
-        f32x4 wd[16];
-        nf_load_w16<8>(wd, Wi, OFF_DIRE / 4 + 16 * 8 * 64, lane);                   // the first direction chunk's weights, a layer ahead
-        nf_seg_lds<NT, 8, true, true>(acc, st, Wi, OFF_DIRE / 4, 16, act4, lane);   // relu(layers_dir.0([feat | dir]))
-        nf_pending_b<NT, true>(bj, st);
-        nf_chunk<NT, 8, false>(acc, st.wb, bj, st.bias);
-        nf_load_w16<8>(st.wb, Wi, OFF_DIRE / 4 + 17 * 8 * 64, lane);
-#pragma unroll
-        for (int t = 0; t < NT; ++t) bj[t] = dirf[t][0];
-        nf_chunk<NT, 8, false>(acc, wd, bj, st.bias);
-#pragma unroll
-        for (int t = 0; t < NT; ++t) bj[t] = dirf[t][1];
-        nf_tail<NT, 8, 8, 1, 1>(acc, st.wb, bj, st, Wi, OFF_RGB / 4, Ci, B_RGB, act4, lane);
-    }
-    nf_seg_lds<NT, 1, true, true>(acc, st, Wi, OFF_RGB / 4, 8, act4, lane);
-    nf_pending_b<NT, true>(bj, st);
-    nf_chunk<NT, 1, false>(acc, st.wb, bj, st.bias);
-    if (g == 0) {
-#pragma unroll
-        for (int t = 0; t < NT; ++t) {
-            const int64_t p = p0 + 16 * t + c;
-            if (p < n_points) reinterpret_cast<f32x4*>(out)[p] = (f32x4){acc[t][0].x, acc[t][0].y, acc[t][0].z, sigma_raw[t]};
-        }
-    }
+    const NfW Wi = nf_w_image(packed, nlc::PACKED), Ci = nf_w_image(cond, nlc::COND_FLOATS);
+    nf_lcode_net_body<NT, 2>(acc, sigma_raw, pe, dirf, Wi, Ci, act4, lane);
+    nf_net_store_raw<NT>(acc, sigma_raw, p0, n_points, lane, out);
 }
-
-int nf_lcode_launch_fwd_encoded(const float* packed, const float* cond, const float* x87, int64_t n_points, float* out, nf_stream_t stream);
 
 // x87: (n_points, 87) pre-encoded inputs; cond: scratch of nf_lcode_cond_floats() floats; out: (n_points, 4).
 extern "C" int nf_lcode_forward_encoded(const float* packed, const float* x87, const float* expr76, const float* latent32,
@@ -277,6 +163,7 @@ k_lcode_mlp_fwd_save(const float* __restrict__ packed, const float* __restrict__
                      const float* __restrict__ rd, const float* __restrict__ rd_view, const float* __restrict__ z, int64_t n_points, int S,
                      float* __restrict__ raw, float* __restrict__ saved) {
     using namespace nlc;
+    using Net = NfLcodeNet;
     static_assert(NT == 2, "the copy schedule below is written for 32-point slabs");
     __shared__ __attribute__((aligned(16))) f32x4 lds[NF_MLP_WAVES * 16 * NT * 64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -288,20 +175,11 @@ k_lcode_mlp_fwd_save(const float* __restrict__ packed, const float* __restrict__
     auto sec = [&](int s_, int width) { return nf_slab_copy(saved, s_, width, p0, n); };
     f32x4 pe[NT][4];
     f32x4 dirf[NT][1];
+    nf_net_inputs<NT>(pe, dirf, p0, n_points, S, lane, ro, rd, rd_view, z);
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
-        int64_t p = p0 + 16 * t + c;
-        if (p >= n_points) p = n_points - 1;
-        const int64_t ray = p / S;
-        const float zz = z[p];
-        const float px = nf_add(ro[ray * 3 + 0], nf_mul(rd[ray * 3 + 0], zz));
-        const float py = nf_add(ro[ray * 3 + 1], nf_mul(rd[ray * 3 + 1], zz));
-        const float pz = nf_add(ro[ray * 3 + 2], nf_mul(rd[ray * 3 + 2], zz));
-        nf_encode_point(px, py, pz, g, pe[t]);
-        float s, cs;
-        nf_sincos(nf_mul(rd_view[ray * 3 + 2], (float)(1 << g)), &s, &cs);
-        dirf[t][0] = (f32x4){s, cs, 0.0f, 0.0f};
-        if (p0 + 16 * t + c < n_points) *reinterpret_cast<f32x4*>(saved + S_DIRF * n_points + p * 16 + 4 * g) = dirf[t][0];
+        const int64_t p = p0 + 16 * t + c;
+        if (p < n) *reinterpret_cast<f32x4*>(saved + S_DIRF * n + p * 16 + 4 * g) = dirf[t][0];
 #pragma unroll
         for (int j = 0; j < 4; ++j) act4[nf_act_idx4(16 * t + c, 4 * j + g)] = pe[t][j];
     }
@@ -320,46 +198,12 @@ k_lcode_mlp_fwd_save(const float* __restrict__ packed, const float* __restrict__
     f32x4 bj[NT];
     float sigma_raw[NT];
     const NfW Wi = nf_w_image(packed, PACKED), Ci = nf_w_image(cond, COND_FLOATS);
-#define NF_PE_B(J_) do { _Pragma("unroll") for (int t = 0; t < NT; ++t) bj[t] = pe[t][J_]; } while (0)
-    // the last chunk's fragment (+ its mask bits), then the finished mask words of ReLU layer MASKL_ (the layer whose output was just consumed)
-#define NF_LC_PENDING(RELU_, MASKL_, NCH_)                                                          \
-    do {                                                                                            \
-        nf_pending_b<NT, RELU_>(bj, st);                                                            \
-        if ((MASKL_) >= 0) {                                                                        \
-            nf_mask_bits<NT>(m64, st.bp, (NCH_) - 2);                                               \
-            nf_mask_bits<NT>(m64, bj, (NCH_) - 1);                                                  \
-            _Pragma("unroll") for (int t = 0; t < NT; ++t)                                          \
-                if (p0 + 16 * t < n)                                                                \
-                    *nf_mask_ptr<S_MASK>(saved, n, (MASKL_) >= 0 ? (MASKL_) : 0, (p0 >> 4) + t, lane) = make_uint2((uint32_t)m64[t], (uint32_t)(m64[t] >> 32)); \
-        }                                                                                           \
-    } while (0)
-    // one 256-wide layer from the slab: the slab = section SEC_ (ReLU layer MASKL_, or -1: as stored) is copied out and consumed
-#define NF_LC_LAYER256(OFF_, SEC_, MASKL_, OFF_NEXT_, B_NEXT_, NO_NEXT_)                                                   \
-    do {                                                                                                                   \
-        NfCopyH<64, 4, ((MASKL_) >= 0)> cs{act4, sec(SEC_, 256), lane, 8, {}};                                             \
-        cs.prime();                                                                                                        \
-        _Pragma("unroll") for (int t = 0; t < NT; ++t) m64[t] = 0;                                                         \
-        nf_seg_lds<NT, 16, true, ((MASKL_) >= 0), ((MASKL_) >= 0)>(acc, st, Wi, OFF_, 16, act4, lane, cs, m64);            \
-        NF_LC_PENDING(((MASKL_) >= 0), MASKL_, 16);                                                                        \
-        nf_tail<NT, 16, 16, NO_NEXT_, 1>(acc, st.wb, bj, st, Wi, OFF_NEXT_, Ci, B_NEXT_, act4, lane);                     \
-    } while (0)
     // ---- layer1 : PE(64 slots) -> 256, no activation (M:609) ---------------------------------------------------------
-    nf_load_bias<16>(st.bias, Ci, B_L1, lane);
-    {
-        f32x4 w[16];
-        nf_load_w16<16>(w, Wi, OFF_L1 / 4, lane);
-        NF_PE_B(0); nf_chunk<NT, 16, true>(acc, w, bj, st.bias);
-        nf_load_w16<16>(w, Wi, OFF_L1 / 4 + 1 * 16 * 64, lane);
-        NF_PE_B(1); nf_chunk<NT, 16, false>(acc, w, bj, st.bias);
-        nf_load_w16<16>(w, Wi, OFF_L1 / 4 + 2 * 16 * 64, lane);
-        NF_PE_B(2); nf_chunk<NT, 16, false>(acc, w, bj, st.bias);
-        nf_load_w16<16>(w, Wi, OFF_L1 / 4 + 3 * 16 * 64, lane);
-        NF_PE_B(3); nf_tail<NT, 16, 16, 16, 1>(acc, w, bj, st, Wi, OFF_X0 / 4, Ci, B_X0, act4, lane);
-    }
+    NF_NET_PE_LAYER(B_L1, OFF_L1, OFF_X0, B_X0);
     // ---- layers_xyz.0 (reads layer1's output as stored), .1, .2 ---------------------------------------------------------
-    NF_LC_LAYER256(OFF_X0 / 4, S_L1, -1, OFF_X1 / 4, B_X1, 16);
-    NF_LC_LAYER256(OFF_X1 / 4, S_X0, 0, OFF_X2 / 4, B_X2, 16);
-    NF_LC_LAYER256(OFF_X2 / 4, S_X1, 1, OFF_ALPHA / 4, B_ALPHA, 1);
+    NF_NET_SAVE_LAYER256(OFF_X0 / 4, true, S_L1, -1, OFF_X1 / 4, B_X1, 16, 1);
+    NF_NET_SAVE_LAYER256(OFF_X1 / 4, true, S_X0, 0, OFF_X2 / 4, B_X2, 16, 1);
+    NF_NET_SAVE_LAYER256(OFF_X2 / 4, true, S_X1, 1, OFF_ALPHA / 4, B_ALPHA, 1, 1);
     // ---- fc_alpha(x2): one tile, stores nothing (the slab stays for fc_feat), copies nothing -------------------------------
     nf_seg_lds<NT, 1, true, true>(acc, st, Wi, OFF_ALPHA / 4, 16, act4, lane);
     nf_pending_b<NT, true>(bj, st);
@@ -367,7 +211,7 @@ k_lcode_mlp_fwd_save(const float* __restrict__ packed, const float* __restrict__
 #pragma unroll
     for (int t = 0; t < NT; ++t) sigma_raw[t] = acc[t][0].x;
     // ---- feat = relu(fc_feat(x2)): x2 is copied and its mask collected here ---------------------------------------------
-    NF_LC_LAYER256(OFF_FEAT / 4, S_X2, 2, OFF_DIR / 4, B_DIR, 8);
+    NF_NET_SAVE_LAYER256(OFF_FEAT / 4, true, S_X2, 2, OFF_DIR / 4, B_DIR, 8, 1);
     // ---- layers_dir.0 : [feat | dir slots] -> 128 ---------------------------------------------------------------------------
     {
         f32x4 wd[16];
@@ -377,7 +221,7 @@ k_lcode_mlp_fwd_save(const float* __restrict__ packed, const float* __restrict__
 #pragma unroll
         for (int t = 0; t < NT; ++t) m64[t] = 0;
         nf_seg_lds<NT, 8, true, true, true>(acc, st, Wi, OFF_DIR / 4, 16, act4, lane, cs, m64);
-        NF_LC_PENDING(true, 3, 16);
+        NF_NET_SAVE_PENDING(true, 3, 16);
         nf_chunk<NT, 8, false>(acc, st.wb, bj, st.bias);
 #pragma unroll
         for (int t = 0; t < NT; ++t) bj[t] = dirf[t][0];
@@ -390,19 +234,10 @@ k_lcode_mlp_fwd_save(const float* __restrict__ packed, const float* __restrict__
 #pragma unroll
         for (int t = 0; t < NT; ++t) m64[t] = 0;
         nf_seg_lds<NT, 1, true, true, true>(acc, st, Wi, OFF_RGB / 4, 8, act4, lane, cs, m64);
-        NF_LC_PENDING(true, 4, 8);
+        NF_NET_SAVE_PENDING(true, 4, 8);
         nf_chunk<NT, 1, false>(acc, st.wb, bj, st.bias);
     }
-#undef NF_LC_LAYER256
-#undef NF_LC_PENDING
-#undef NF_PE_B
-    if (g == 0) {
-#pragma unroll
-        for (int t = 0; t < NT; ++t) {
-            const int64_t p = p0 + 16 * t + c;
-            if (p < n_points) reinterpret_cast<f32x4*>(raw)[p] = (f32x4){acc[t][0].x, acc[t][0].y, acc[t][0].z, sigma_raw[t]};
-        }
-    }
+    nf_net_store_raw<NT>(acc, sigma_raw, p0, n_points, lane, raw);
 }
 
 static int nf_lcode_launch_fwd(const float* packed, const float* cond, const float* ro, const float* rd, const float* rd_view,

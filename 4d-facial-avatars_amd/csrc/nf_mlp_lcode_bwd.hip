@@ -8,12 +8,7 @@
 //                              expression / latent / (near, far) columns as outer products) + d latent = W1[:,139:171]^T db1
 #include <vector>
 #include <mutex>
-#include "nf_mlp_dev.h"
-#include "nf_mlp_stream.h"
-#include "nf_mlp_lcode_layout.h"
-#include "nf_mlp_bwd.h"
-#include "nf_pack.h"
-
+#include "nf_mlp_lcode_net_bwd.h"
 
 // =================================================================================================
 // transposed pack: block (ni, no), lane (g, i), r -> W[row = 16 ni + 4 g + r][col = 16 no + i]
@@ -45,72 +40,19 @@ extern "C" int nf_lcode_pack_bwd(const float* const* params, float* packed_t, nf
 // =================================================================================================
 // B1: backward chain
 // =================================================================================================
-template <int NT, int NO>
-__device__ __forceinline__ void nf_lc_zero_acc(f32x4 (&acc)[NT][16]) {
-#pragma unroll
-    for (int no = 0; no < NO; ++no)
-#pragma unroll
-        for (int t = 0; t < NT; ++t) acc[t][no] = (f32x4){0.f, 0.f, 0.f, 0.f};
-}
-
-// Layer-streamed like the paper model's chain (nf_mlp_bwd.hip: k_paper_mlp_bwd_chain_masks; nf_mlp_stream.h: nf_seg_lds, nf_tail_dz):
-// C = 0 as the C operand of a layer's first MFMAs, the slab copied to `dz` from inside the K loops, the masked layer boundary under the
-// last chunk, a layer's two mask words fetched when its loop starts.
+// The layer list on the shared chain text (nf_mlp_net_common.h: NF_NET_CHAIN_*), like the paper model's (nf_mlp_paper_net_bwd.h).
+// ReLU layers: layers_xyz.0..2 -> 0..2, fc_feat -> 3, layers_dir.0 -> 4.
 template <int NT>
 __global__ void __launch_bounds__(64 * NF_MLP_WAVES, 1)
 k_lcode_mlp_bwd_chain(const float* __restrict__ packed_t, const float* __restrict__ saved, const float* __restrict__ d_raw,
                       int64_t n_points, float* __restrict__ dz) {
     using namespace nlc;
-    static_assert(NT == 2, "the copy schedule below is written for 32-point slabs");
+    using Net = NfLcodeNet;
     __shared__ __attribute__((aligned(16))) f32x4 lds[NF_MLP_WAVES * 16 * NT * 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int g = lane >> 4, c = lane & 15;
-    const int64_t p0 = ((int64_t)blockIdx.x * NF_MLP_WAVES + wave) * (16 * NT);
-    if (p0 >= n_points) return;
-    f32x4* act4 = lds + wave * (16 * NT * 64);
-    const int64_t n = n_points;
-    const NfW Wi = nf_w_image(packed_t, PACKED_T);
-    auto sec = [&](int zs, int width) { return nf_slab_copy(dz, zs, width, p0, n); };
-    auto masks = [&](int l, uint2 (&m)[NT]) {           // layers_xyz.0..2 -> 0..2, fc_feat -> 3, layers_dir.0 -> 4
-#pragma unroll
-        for (int t = 0; t < NT; ++t)
-            m[t] = p0 + 16 * t < n ? *nf_mask_ptr<S_MASK>(const_cast<float*>(saved), n, l, (p0 >> 4) + t, lane) : make_uint2(0u, 0u);
-    };
-    f32x4 frag_rgb[NT][1], frag_sig[NT];
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-        const int64_t p = p0 + 16 * t + c;
-        f32x4 d = (f32x4){0.f, 0.f, 0.f, 0.f};
-        if (p < n && g == 0) d = reinterpret_cast<const f32x4*>(d_raw)[p];
-        frag_rgb[t][0] = (f32x4){d.x, d.y, d.z, 0.f};
-        frag_sig[t] = (f32x4){d.w, 0.f, 0.f, 0.f};
-    }
-    f32x4 acc[NT][16];
-    NfStream<NT> st;
-    f32x4 bj[NT];
-    uint64_t unused64[NT];
-    uint2 m[NT];
-#pragma unroll
-    for (int no = 0; no < 16; ++no) st.bias[no] = (f32x4){0.f, 0.f, 0.f, 0.f};      // C = 0
-    // d(layers_dir.0 out) = d rgb . fc_rgb.weight, masked by its ReLU: one register chunk, the round-3 form
-    masks(4, m);
-    nf_lc_zero_acc<NT, 8>(acc);
-    nf_mma_from_regs<NT, 8, 1>(acc, reinterpret_cast<const f32x4*>(packed_t) + OFFT_RGB / 4, frag_rgb, lane);
-    nf_apply_mask<NT, 8>(acc, m);
-    nf_store_act<NT, 8, false>(acc, act4, lane);
-    nf_load_w16<16>(st.wa, Wi, OFFT_DIR / 4, lane);
-    nf_read_b<NT>(st.b0, act4, lane, 0);
-#define NF_LC_CHAIN_LAYER(OFF_, NCH_, W4_, ZSEC_, MASKL_, OFF_NEXT_, NO_NEXT_)                                         \
-    do {                                                                                                             \
-        NfCopyH<W4_, 4, false> cs{act4, sec(ZSEC_, 4 * (W4_)), lane, (NCH_) / 2, {}};                                  \
-        cs.prime();                                                                                                  \
-        if ((MASKL_) >= 0) masks((MASKL_) >= 0 ? (MASKL_) : 0, m);                                                   \
-        nf_seg_lds<NT, 16, true, false, false>(acc, st, Wi, OFF_, NCH_, act4, lane, cs, unused64);                   \
-        nf_pending_b<NT, false>(bj, st);                                                                             \
-        nf_tail_dz<NT, 16, NO_NEXT_, ((MASKL_) >= 0)>(acc, st.wb, bj, st, Wi, OFF_NEXT_, act4, lane, m);             \
-    } while (0)
+    // d(layers_dir.0 out) = d rgb . fc_rgb.weight, masked by its ReLU
+    NF_NET_CHAIN_BEGIN(4, OFFT_DIR / 4, 16);
     // d feat = dZ_dir . layers_dir.0.weight[:, :256], masked by relu(fc_feat)
-    NF_LC_CHAIN_LAYER(OFFT_DIR / 4, 8, 32, Z_DIR, 3, OFFT_FEAT / 4, 16);
+    NF_NET_CHAIN_LAYER(OFFT_DIR / 4, 16, 8, 32, Z_DIR, 3, OFFT_FEAT / 4, 16);
     // d x2 = dZ_feat . fc_feat.weight + d sigma * fc_alpha.weight, masked by layers_xyz.2's ReLU: 16 slab chunks + one register chunk
     {
         f32x4 wd[16];
@@ -123,15 +65,10 @@ k_lcode_mlp_bwd_chain(const float* __restrict__ packed_t, const float* __restric
         nf_chunk<NT, 16, false>(acc, st.wb, bj, st.bias);
         nf_tail_dz<NT, 16, 16, true>(acc, wd, frag_sig, st, Wi, OFFT_X2 / 4, act4, lane, m);
     }
-    NF_LC_CHAIN_LAYER(OFFT_X2 / 4, 16, 64, Z_X2, 1, OFFT_X1 / 4, 16);
-    NF_LC_CHAIN_LAYER(OFFT_X1 / 4, 16, 64, Z_X1, 0, OFFT_X0 / 4, 16);
-    NF_LC_CHAIN_LAYER(OFFT_X0 / 4, 16, 64, Z_X0, -1, 0, 0);              // d(layer1 out): layer1 has no activation (M:609)
-#undef NF_LC_CHAIN_LAYER
-    {   // the last section has no K loop behind it
-        const NfSlabCopy cp = sec(Z_L1, 256);
-#pragma unroll 4
-        for (int k = 0; k < 16 * NT; ++k) nf_copy_rows<64>(act4, cp, k, lane);
-    }
+    NF_NET_CHAIN_LAYER(OFFT_X2 / 4, 16, 16, 64, Z_X2, 1, OFFT_X1 / 4, 16);
+    NF_NET_CHAIN_LAYER(OFFT_X1 / 4, 16, 16, 64, Z_X1, 0, OFFT_X0 / 4, 16);
+    NF_NET_CHAIN_LAYER(OFFT_X0 / 4, 16, 16, 64, Z_X0, -1, 0, 0);              // d(layer1 out): layer1 has no activation (M:609)
+    NF_NET_CHAIN_END(Z_L1);
 }
 
 // =================================================================================================
@@ -199,72 +136,18 @@ static void nf_lcode_build_dw_groups(NfDwGroup* gr) {
 // =================================================================================================
 // B3, second half: scatter to the reference parameter layout (order = nerf.models.LCODE_KEYS)
 // =================================================================================================
-struct NfLcodeGradOffsets { int off[nlc::NPARAMS + 1]; };
-
+// the last workgroup: d latent_j = sum_n layer1.weight[n][139 + j] * d b1[n]
 __global__ void __launch_bounds__(256) k_lcode_grad_unpack(const float* __restrict__ sum, const float* __restrict__ packed,
-                                                           const float* __restrict__ cond, NfLcodeGradOffsets offs,
+                                                           const float* __restrict__ cond, NfLcodeGradOffsets<171> offs,
                                                            float* __restrict__ grads) {
     using namespace nlc;
-    const float* cvec = cond + B_CVEC;
-    const float* dvec = cond + B_DVEC;
     if (blockIdx.x == gridDim.x - 1) {
-        // d latent_j = sum_n layer1.weight[n][139 + j] * d b1[n], the last workgroup's job (one thread per j through 256 dependent trips was
-        // the longest path of the launch): thread (q, j) sums n = 32 q .. 32 q + 31, the eight partial sums are added in a fixed order
-        __shared__ float part[8][32];
-        const int j = (int)threadIdx.x & 31, q = (int)threadIdx.x >> 5;
-        const float* w1 = packed + OFF_WC1 + 76 + j;
-        float v = 0.f;
-#pragma unroll 8
-        for (int n = 32 * q; n < 32 * q + 32; ++n) v += w1[n * 108] * sum[CS_L1 + n];
-        part[q][j] = v;
-        __syncthreads();
-        if (threadIdx.x < 32) {
-            float r = part[0][j];
-#pragma unroll
-            for (int k = 1; k < 8; ++k) r += part[k][j];
-            grads[GRAD_PARAM_FLOATS + j] = r;
-        }
+        nf_lcode_dcond(packed, sum, 76, 32, grads + GRAD_PARAM_FLOATS);
         return;
     }
-    for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < GRAD_PARAM_FLOATS; e += (gridDim.x - 1) * blockDim.x) {
-        float v = 0.f;
-        int t = 0;
-        while (e >= offs.off[t + 1]) ++t;
-        const int local = e - offs.off[t];
-        switch (t) {
-            case 0: {  // layer1.weight [256][171] = [pe 63 | expr/3 76 | latent 32]
-                const int n = local / 171, col = local - 171 * n;
-                v = col < 63 ? sum[G_L1 + n * 64 + nfl::pe_col_to_slot(col)] : sum[CS_L1 + n] * cvec[col - 63];
-            } break;
-            case 1: v = sum[CS_L1 + local]; break;
-            case 2: v = sum[G_X0 + local]; break;
-            case 3: v = sum[CS_L1 + 256 + local]; break;
-            case 4: v = sum[G_X1 + local]; break;
-            case 5: v = sum[CS_L1 + 512 + local]; break;
-            case 6: v = sum[G_X2 + local]; break;
-            case 7: v = sum[CS_L1 + 768 + local]; break;
-            case 8: {  // layers_dir.0.weight [128][280] = [feat 256 | PE4(rd_z, near, far) 24]
-                const int n = local / 280, col = local - 280 * n;
-                if (col < 256) v = sum[G_DIRA + n * 256 + col];
-                else {
-                    const int q = col - 256, f = q / 6, rem = q - 6 * f, sc = rem / 3, comp = rem - 3 * sc;
-                    v = comp == 0 ? sum[G_DIRB + n * 16 + 4 * f + sc] : sum[CS_DIR + n] * dvec[4 * f + 2 * sc + (comp - 1)];
-                }
-            } break;
-            case 9: v = sum[CS_DIR + local]; break;
-            case 10: v = sum[G_ALPHA + 3 * 256 + local]; break;   // fc_alpha.weight [1][256] = row 3 (d sigma) of d_raw^T x
-            case 11: v = sum[CS_RGB + 3]; break;
-            case 12: v = sum[G_RGB + local]; break;               // fc_rgb.weight [3][128]
-            case 13: v = sum[CS_RGB + local]; break;
-            case 14: v = sum[G_FEAT + local]; break;
-            case 15: v = sum[CS_L1 + 1024 + local]; break;
-        }
-        grads[e] = v;
-    }
+    for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < GRAD_PARAM_FLOATS; e += (gridDim.x - 1) * blockDim.x)
+        grads[e] = nf_lcode_trunk_grad<171>(e, offs, sum, cond + B_CVEC, cond + B_DVEC);
 }
-
-static const int NF_LC_PARAM_NUMEL[nlc::NPARAMS] = {256 * 171, 256, 65536, 256, 65536, 256, 65536, 256,   // layer1, layers_xyz.0..2
-                                                     128 * 280, 128, 256, 1, 384, 3, 65536, 256};          // layers_dir.0, fc_alpha, fc_rgb, fc_feat
 
 extern "C" size_t nf_lcode_grad_floats(void) { return (size_t)nlc::GRAD_FLOATS; }
 
@@ -292,10 +175,8 @@ static void nf_lcode_dw_f32(const NfDwGroupSet& gset, const float* dz, const flo
 static void nf_lcode_reduce_unpack(const float* slabs, int ns, const NfReduceAlt& alt, float* sum, const float* packed, const float* cond,
                                    float* grads, hipStream_t s) {
     hipLaunchKernelGGL((k_grad_reduce<1>), dim3(512), dim3(256), 0, s, slabs, ns, (int)nlc::SLAB_FLOATS, sum, alt);
-    NfLcodeGradOffsets offs;
-    offs.off[0] = 0;
-    for (int i = 0; i < nlc::NPARAMS; ++i) offs.off[i + 1] = offs.off[i] + NF_LC_PARAM_NUMEL[i];
-    hipLaunchKernelGGL(k_lcode_grad_unpack, dim3(1024 + 1), dim3(256), 0, s, sum, packed, cond, offs, grads);      // + 1: the d-latent workgroup
+    hipLaunchKernelGGL(k_lcode_grad_unpack, dim3(1024 + 1), dim3(256), 0, s, sum, packed, cond, nf_lcode_grad_offsets<171>(),
+                       grads);                                                                                      // + 1: the d-latent workgroup
 }
 
 static const NfBwdFamily nf_lcode_bwd = {1, nlc::DZ_PER_POINT, nlc::SLAB_FLOATS, NF_LC_DW_GROUPS, nf_lcode_build_dw_groups,

@@ -4,11 +4,11 @@
 // struct over its layout namespace plus two discriminators:
 //   HAS_L5   the 256-wide hidden layer layers_xyz.5 exists (and with it tensor ids, sections and ReLU layers behind layers_xyz.4 shift)
 //   D0_EXPR  the 76 expression columns enter layers_dir.0 a second time (folded into its bias; its weight is [128][D0_COLS])
-// This header holds the forward half: gather table, bias-table (condition) kernel body, input fragments, the inference and the saving
-// layer stream.  The __global__ kernels keep their names in their translation units and wrap these.  Backward: nf_mlp_paper_net_bwd.h.
+// This header holds the forward half: gather table, bias-table (condition) kernel body, the inference and the saving layer stream.
+// The __global__ kernels keep their names in their translation units and wrap these.  Backward: nf_mlp_paper_net_bwd.h.  Input
+// fragments, the `raw` store and the stream text shared with the second family's network: nf_mlp_net_common.h.
 #pragma once
-#include "nf_mlp_dev.h"
-#include "nf_mlp_stream.h"
+#include "nf_mlp_net_common.h"
 #include "nf_mlp_smaller_layout.h"
 #include "nf_pack.h"
 
@@ -188,105 +188,19 @@ static inline dim3 nf_paper_net_condition_grid() { return dim3((Net::COND_FLOATS
 // =================================================================================================
 // forward
 // =================================================================================================
-// inputs of one wave from rays: pts = ro + rd*z (T:78), PE fragments, dir fragment
-template <int NT>
-__device__ __forceinline__ void nf_paper_net_inputs(f32x4 (&pe)[NT][4], f32x4 (&dirf)[NT][1], int64_t p0, int64_t n_points, int S, int lane,
-                                                    const float* __restrict__ ro, const float* __restrict__ rd,
-                                                    const float* __restrict__ rd_view, const float* __restrict__ z) {
-    const int g = lane >> 4, c = lane & 15;
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-        int64_t p = p0 + 16 * t + c;
-        if (p >= n_points) p = n_points - 1;
-        const int64_t ray = p / S;
-        const float zz = z[p];
-        const float dx = rd[ray * 3 + 0], dy = rd[ray * 3 + 1], dz = rd[ray * 3 + 2];
-        const float px = nf_add(ro[ray * 3 + 0], nf_mul(dx, zz));
-        const float py = nf_add(ro[ray * 3 + 1], nf_mul(dy, zz));
-        const float pz = nf_add(ro[ray * 3 + 2], nf_mul(dz, zz));
-        nf_encode_point(px, py, pz, g, pe[t]);
-        float s, cs;
-        nf_sincos(nf_mul(rd_view[ray * 3 + 2], (float)(1 << g)), &s, &cs);   // Quirk Q1: "direction" = (rd_z, near, far)
-        dirf[t][0] = (f32x4){s, cs, 0.0f, 0.0f};
-    }
-}
-
-// inputs of one wave from PRE-ENCODED rows x87 (P, 87) = [PE10(xyz) (63) | PE4(dirs) (24)]: the PE fragments in slot order and the 24
-// direction columns in reference order as two register chunks
-template <int NT>
-__device__ __forceinline__ void nf_paper_net_inputs_encoded(f32x4 (&pe)[NT][4], f32x4 (&dirf)[NT][2], int64_t p0, int64_t n_points, int lane,
-                                                            const float* __restrict__ x87) {
-    const int g = lane >> 4, c = lane & 15;
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-        int64_t p = p0 + 16 * t + c;
-        if (p >= n_points) p = n_points - 1;
-        const float* row = x87 + p * 87;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            float v[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int col = nfl::pe_slot_to_col(16 * j + 4 * g + r);
-                v[r] = col >= 0 ? row[col] : 0.0f;
-            }
-            pe[t][j] = (f32x4){v[0], v[1], v[2], v[3]};
-        }
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            float v[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int s = 16 * j + 4 * g + r;
-                v[r] = s < 24 ? row[63 + s] : 0.0f;
-            }
-            dirf[t][j] = (f32x4){v[0], v[1], v[2], v[3]};
-        }
-    }
-}
-
-// rgb_raw / sigma_raw of the wave's points -> out (n_points, 4): lane group 0 holds them
-template <int NT>
-__device__ __forceinline__ void nf_paper_net_store_raw(const f32x4 (&acc)[NT][16], const float (&sigma_raw)[NT], int64_t p0, int64_t n_points,
-                                                       int lane, float* __restrict__ out) {
-    const int g = lane >> 4, c = lane & 15;
-    if (g == 0) {
-#pragma unroll
-        for (int t = 0; t < NT; ++t) {
-            const int64_t p = p0 + 16 * t + c;
-            if (p < n_points) reinterpret_cast<f32x4*>(out)[p] = (f32x4){acc[t][0].x, acc[t][0].y, acc[t][0].z, sigma_raw[t]};
-        }
-    }
-}
-
-#define NF_PE_B(J_) do { _Pragma("unroll") for (int t = 0; t < NT; ++t) bj[t] = pe[t][J_]; } while (0)
-// layers_xyz.0 : PE(64 slots) -> 256, four register chunks; ends in the tail that fetches layers_xyz.1
-#define NF_NET_L0()                                                                                           \
-    do {                                                                                                      \
-        nf_load_bias<16>(st.bias, Ci, Net::B_L0, lane);                                                       \
-        f32x4 w[16];                                                                                          \
-        nf_load_w16<16>(w, Wi, Net::OFF_L0 / 4, lane);                                                        \
-        NF_PE_B(0); nf_chunk<NT, 16, true>(acc, w, bj, st.bias);                                              \
-        nf_load_w16<16>(w, Wi, Net::OFF_L0 / 4 + 1 * 16 * 64, lane);                                          \
-        NF_PE_B(1); nf_chunk<NT, 16, false>(acc, w, bj, st.bias);                                             \
-        nf_load_w16<16>(w, Wi, Net::OFF_L0 / 4 + 2 * 16 * 64, lane);                                          \
-        NF_PE_B(2); nf_chunk<NT, 16, false>(acc, w, bj, st.bias);                                             \
-        nf_load_w16<16>(w, Wi, Net::OFF_L0 / 4 + 3 * 16 * 64, lane);                                          \
-        NF_PE_B(3); nf_tail<NT, 16, 16, 16, 1>(acc, w, bj, st, Wi, Net::OFF_L1 / 4, Ci, Net::B_L1, act4, lane); \
-    } while (0)
 // the PE part of layers_xyz.3 : [PE | h] -> 256 (skip connection): four register chunks in front of the 16 slab chunks
 #define NF_NET_L3_PE()                                                                                        \
     do {                                                                                                      \
-        NF_PE_B(0); nf_chunk<NT, 16, true>(acc, st.wa, bj, st.bias);                                          \
+        NF_NET_PE_B(0); nf_chunk<NT, 16, true>(acc, st.wa, bj, st.bias);                                          \
         nf_load_w16<16>(st.wa, Wi, Net::OFF_L3 / 4 + 4 * 16 * 64, lane);   /* the first slab chunk, three chunks ahead */ \
         nf_read_b<NT>(st.b0, act4, lane, 0);                                                                  \
         f32x4 w[16];                                                                                          \
         nf_load_w16<16>(w, Wi, Net::OFF_L3 / 4 + 1 * 16 * 64, lane);                                          \
-        NF_PE_B(1); nf_chunk<NT, 16, false>(acc, w, bj, st.bias);                                             \
+        NF_NET_PE_B(1); nf_chunk<NT, 16, false>(acc, w, bj, st.bias);                                             \
         nf_load_w16<16>(w, Wi, Net::OFF_L3 / 4 + 2 * 16 * 64, lane);                                          \
-        NF_PE_B(2); nf_chunk<NT, 16, false>(acc, w, bj, st.bias);                                             \
+        NF_NET_PE_B(2); nf_chunk<NT, 16, false>(acc, w, bj, st.bias);                                             \
         nf_load_w16<16>(w, Wi, Net::OFF_L3 / 4 + 3 * 16 * 64, lane);                                          \
-        NF_PE_B(3); nf_chunk<NT, 16, false>(acc, w, bj, st.bias);                                             \
+        NF_NET_PE_B(3); nf_chunk<NT, 16, false>(acc, w, bj, st.bias);                                             \
     } while (0)
 
 // The network from layers_xyz.0 to fc_rgb on the inference schedule, shared by the ray-input kernels and the pre-encoded ones:
@@ -308,7 +222,7 @@ __device__ __forceinline__ void nf_paper_net_body(f32x4 (&acc)[NT][16], float (&
     nf_seg_lds<NT, 16, FIRST_, true>(acc, st, Wi, OFF_, 16, act4, lane);                                                    \
     nf_pending_b<NT, true>(bj, st);                                                                                         \
     nf_tail<NT, 16, 16, NO_NEXT_, NEXT_B_>(acc, st.wb, bj, st, Wi, OFF_NEXT_, Ci, B_NEXT_, act4, lane)
-    NF_NET_L0();
+    NF_NET_PE_LAYER(Net::B_L0, Net::OFF_L0, Net::OFF_L1, Net::B_L1);
     NF_NET_LAYER256(Net::OFF_L1 / 4, true, Net::OFF_L2 / 4, Net::B_L2, 16, 1);
     NF_NET_LAYER256(Net::OFF_L2 / 4, true, Net::OFF_L3 / 4, Net::B_L3, 16, 0);
     NF_NET_L3_PE();
@@ -390,12 +304,12 @@ __device__ __forceinline__ void nf_paper_net_fwd_encoded(f32x4* lds, const float
     f32x4* act4 = lds + wave * (16 * NT * 64);
     f32x4 pe[NT][4];
     f32x4 dirf[NT][2];
-    nf_paper_net_inputs_encoded<NT>(pe, dirf, p0, n_points, lane, x87);
+    nf_net_inputs_encoded<NT>(pe, dirf, p0, n_points, lane, x87);
     f32x4 acc[NT][16];
     float sigma_raw[NT];
     const NfW Wi = nf_w_image(packed, Net::PACKED), Ci = nf_w_image(cond, Net::COND_FLOATS);
     nf_paper_net_body<Net, NT, 2>(acc, sigma_raw, pe, dirf, Wi, Ci, act4, lane);
-    nf_paper_net_store_raw<NT>(acc, sigma_raw, p0, n_points, lane, out);
+    nf_net_store_raw<NT>(acc, sigma_raw, p0, n_points, lane, out);
 }
 
 // x87: (n_points, 87) pre-encoded inputs; cond: scratch of the family's cond_floats; out: (n_points, 4).  `condition` / `forward`: the
@@ -443,48 +357,26 @@ __device__ __forceinline__ void nf_paper_net_body_save(f32x4 (&acc)[NT][16], flo
     uint64_t m64[NT];
     NfStream<NT> st;
     f32x4 bj[NT];
-    // the last chunk's fragment (+ its mask bits), then the finished mask words of layer MASKL_ (the layer whose output was just consumed)
-#define NF_NET_PENDING(RELU_, MASKL_, NCH_)                                                          \
-    do {                                                                                            \
-        nf_pending_b<NT, RELU_>(bj, st);                                                            \
-        if ((MASKL_) >= 0) {                                                                        \
-            nf_mask_bits<NT>(m64, st.bp, (NCH_) - 2);                                               \
-            nf_mask_bits<NT>(m64, bj, (NCH_) - 1);                                                  \
-            _Pragma("unroll") for (int t = 0; t < NT; ++t)                                          \
-                if (p0 + 16 * t < n)                                                                \
-                    *nf_mask_ptr<Net::S_MASK>(saved, n, (MASKL_) >= 0 ? (MASKL_) : 0, (p0 >> 4) + t, lane) = make_uint2((uint32_t)m64[t], (uint32_t)(m64[t] >> 32)); \
-        }                                                                                           \
-    } while (0)
-    // one 256-wide layer from the slab: the slab = section SEC_ (ReLU layer MASKL_, or -1: as stored) is copied out and consumed
-#define NF_NET_LAYER256(OFF_, FIRST_, SEC_, MASKL_, OFF_NEXT_, B_NEXT_, NO_NEXT_, NEXT_B_)                                \
-    do {                                                                                                                   \
-        NfCopyH<64, 4, ((MASKL_) >= 0)> cs{act4, sec(SEC_, 256), lane, 8, {}};                                             \
-        cs.prime();                                                                                                        \
-        _Pragma("unroll") for (int t = 0; t < NT; ++t) m64[t] = 0;                                                         \
-        nf_seg_lds<NT, 16, FIRST_, ((MASKL_) >= 0), ((MASKL_) >= 0)>(acc, st, Wi, OFF_, 16, act4, lane, cs, m64);          \
-        NF_NET_PENDING(((MASKL_) >= 0), MASKL_, 16);                                                                       \
-        nf_tail<NT, 16, 16, NO_NEXT_, NEXT_B_>(acc, st.wb, bj, st, Wi, OFF_NEXT_, Ci, B_NEXT_, act4, lane);               \
-    } while (0)
     // one 128-wide layer's K loop (two rows per copy instruction); its tail follows
 #define NF_NET_LAYER128(OFF_, NO_, SEC_, MASKL_)                                                                          \
     NfCopyH<32, 4, true> cs{act4, sec(SEC_, 128), lane, 4, {}};                                                            \
     cs.prime();                                                                                                            \
     _Pragma("unroll") for (int t = 0; t < NT; ++t) m64[t] = 0;                                                             \
     nf_seg_lds<NT, NO_, true, true, true>(acc, st, Wi, OFF_, 8, act4, lane, cs, m64);                                      \
-    NF_NET_PENDING(true, MASKL_, 8)
-    NF_NET_L0();
+    NF_NET_SAVE_PENDING(true, MASKL_, 8)
+    NF_NET_PE_LAYER(Net::B_L0, Net::OFF_L0, Net::OFF_L1, Net::B_L1);
     // ---- layers_xyz.1, .2 (each K loop also streams the layer output it consumes to `saved`), .3 (skip), .4 (, .5), fc_feat ------
-    NF_NET_LAYER256(Net::OFF_L1 / 4, true, Net::S_H0, 0, Net::OFF_L2 / 4, Net::B_L2, 16, 1);
-    NF_NET_LAYER256(Net::OFF_L2 / 4, true, Net::S_H1, 1, Net::OFF_L3 / 4, Net::B_L3, 16, 0);
+    NF_NET_SAVE_LAYER256(Net::OFF_L1 / 4, true, Net::S_H0, 0, Net::OFF_L2 / 4, Net::B_L2, 16, 1);
+    NF_NET_SAVE_LAYER256(Net::OFF_L2 / 4, true, Net::S_H1, 1, Net::OFF_L3 / 4, Net::B_L3, 16, 0);
     NF_NET_L3_PE();
-    NF_NET_LAYER256(Net::OFF_L3 / 4 + 4 * 16 * 64, false, Net::S_H2, 2, Net::OFF_L4 / 4, Net::B_L4, 16, 1);
+    NF_NET_SAVE_LAYER256(Net::OFF_L3 / 4 + 4 * 16 * 64, false, Net::S_H2, 2, Net::OFF_L4 / 4, Net::B_L4, 16, 1);
     if constexpr (Net::HAS_L5) {
-        NF_NET_LAYER256(Net::OFF_L4 / 4, true, Net::S_H3, 3, Net::OFF_L5 / 4, Net::B_L5, 16, 1);
-        NF_NET_LAYER256(Net::OFF_L5 / 4, true, Net::S_H4, 4, Net::OFF_FEAT / 4, Net::B_FEAT, 16, 1);
-        NF_NET_LAYER256(Net::OFF_FEAT / 4, true, Net::S_H5, 5, Net::OFF_D0 / 4, Net::B_D0, 9, 1);
+        NF_NET_SAVE_LAYER256(Net::OFF_L4 / 4, true, Net::S_H3, 3, Net::OFF_L5 / 4, Net::B_L5, 16, 1);
+        NF_NET_SAVE_LAYER256(Net::OFF_L5 / 4, true, Net::S_H4, 4, Net::OFF_FEAT / 4, Net::B_FEAT, 16, 1);
+        NF_NET_SAVE_LAYER256(Net::OFF_FEAT / 4, true, Net::S_H5, 5, Net::OFF_D0 / 4, Net::B_D0, 9, 1);
     } else {
-        NF_NET_LAYER256(Net::OFF_L4 / 4, true, Net::S_H3, 3, Net::OFF_FEAT / 4, Net::B_FEAT, 16, 1);
-        NF_NET_LAYER256(Net::OFF_FEAT / 4, true, Net::S_H4, 4, Net::OFF_D0 / 4, Net::B_D0, 9, 1);
+        NF_NET_SAVE_LAYER256(Net::OFF_L4 / 4, true, Net::S_H3, 3, Net::OFF_FEAT / 4, Net::B_FEAT, 16, 1);
+        NF_NET_SAVE_LAYER256(Net::OFF_FEAT / 4, true, Net::S_H4, 4, Net::OFF_D0 / 4, Net::B_D0, 9, 1);
     }
     // ---- layers_dir.0 : [feat | dir slots] -> 128; tile 8 row 0 = fc_alpha(feat) (Q2); fc_feat has no activation ------------------
     {
@@ -493,7 +385,7 @@ __device__ __forceinline__ void nf_paper_net_body_save(f32x4 (&acc)[NT][16], flo
         NfCopyH<64, 4, false> cs{act4, sec(Net::S_FEAT, 256), lane, 8, {}};
         cs.prime();
         nf_seg_lds<NT, 9, true, false, false>(acc, st, Wi, Net::OFF_D0 / 4, 16, act4, lane, cs, m64);
-        NF_NET_PENDING(false, -1, 16);
+        NF_NET_SAVE_PENDING(false, -1, 16);
         nf_chunk<NT, 9, false>(acc, st.wb, bj, st.bias);
 #pragma unroll
         for (int t = 0; t < NT; ++t) bj[t] = dirf[t][0];
@@ -515,12 +407,8 @@ __device__ __forceinline__ void nf_paper_net_body_save(f32x4 (&acc)[NT][16], flo
         nf_chunk<NT, 1, false>(acc, st.wb, bj, st.bias);
     }
 #undef NF_NET_LAYER128
-#undef NF_NET_LAYER256
-#undef NF_NET_PENDING
 }
 #undef NF_NET_L3_PE
-#undef NF_NET_L0
-#undef NF_PE_B
 
 template <class Net, int NT>
 __device__ __forceinline__ void nf_paper_net_fwd_save(f32x4* lds, const float* __restrict__ packed, const float* __restrict__ cond,
@@ -533,12 +421,12 @@ __device__ __forceinline__ void nf_paper_net_fwd_save(f32x4* lds, const float* _
     f32x4* act4 = lds + wave * (16 * NT * 64);
     f32x4 pe[NT][4];
     f32x4 dirf[NT][1];
-    nf_paper_net_inputs<NT>(pe, dirf, p0, n_points, S, lane, ro, rd, rd_view, z);
+    nf_net_inputs<NT>(pe, dirf, p0, n_points, S, lane, ro, rd, rd_view, z);
     f32x4 acc[NT][16];
     float sigma_raw[NT];
     const NfW Wi = nf_w_image(packed, Net::PACKED), Ci = nf_w_image(cond, Net::COND_FLOATS);
     nf_paper_net_body_save<Net, NT>(acc, sigma_raw, pe, dirf, Wi, Ci, act4, lane, saved, p0, n_points);
-    nf_paper_net_store_raw<NT>(acc, sigma_raw, p0, n_points, lane, raw);
+    nf_net_store_raw<NT>(acc, sigma_raw, p0, n_points, lane, raw);
 }
 
 // Launch of a family's ray-input forward: `fwd` = its k_*_mlp_fwd<NF_MLP_NT> (inference: a persistent grid, at most one workgroup per
@@ -586,7 +474,7 @@ __device__ __forceinline__ void nf_paper_net_fwd_sigma(f32x4* lds, const float* 
         const float* cond = cond_ + opaque0;
         f32x4 pe[NT][4];
         f32x4 dirf[NT][1];
-        nf_paper_net_inputs<NT>(pe, dirf, p0, n_points, S, lane, ro, rd, rd, z_v);
+        nf_net_inputs<NT>(pe, dirf, p0, n_points, S, lane, ro, rd, rd, z_v);
         f32x4 acc[NT][16];
         float sigma_raw[NT];
         const NfW Wi = nf_w_image(W, Net::PACKED), Ci = nf_w_image(cond, Net::COND_FLOATS);

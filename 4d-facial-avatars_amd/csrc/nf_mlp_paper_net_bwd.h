@@ -29,66 +29,17 @@ static void nf_paper_net_table_t(std::vector<uint32_t>& t) {
 // =================================================================================================
 // B1: backward chain of one wave
 // =================================================================================================
-// dZ_D2 -> dZ_D1 -> dZ_D0 -> d feat (+ d sigma * fc_alpha.weight) -> (dZ_L5 ->) dZ_L4 -> ... -> dZ_L0 on the forward kernels' streamed K
-// loops (nf_mlp_stream.h: nf_seg_lds, nf_tail_dz): C = 0 is the C operand of a layer's first MFMAs, the copy of the slab to `dz` rides in
-// the loops (whole lines through a range-checked descriptor), the layer boundary sits under the last chunk's MFMAs with the ReLU mask
-// applied on the way to the slab, and a layer's two mask words (saved by the training forward) are fetched when its loop starts.
+// dZ_D2 -> dZ_D1 -> dZ_D0 -> d feat (+ d sigma * fc_alpha.weight) -> (dZ_L5 ->) dZ_L4 -> ... -> dZ_L0: the layer list on the shared
+// chain text (nf_mlp_net_common.h: NF_NET_CHAIN_*).
 // Against the earlier block epilogue: 1.87 -> 1.78-1.80 ms per 262144 points, bit-identical (profiles/r04_experiments.md section 8).
 template <class Net, int NT>
 __device__ __forceinline__ void nf_paper_net_bwd_chain(f32x4* lds, const float* __restrict__ packed_t, const float* __restrict__ saved,
                                                        const float* __restrict__ d_raw, int64_t n_points, float* __restrict__ dz) {
-    static_assert(NT == 2, "the copy schedule below is written for 32-point slabs");
     constexpr int NX = nf_net_n_xyz<Net>;             // ReLU layers: layers_xyz.l -> l, layers_dir.d -> NX + d
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int g = lane >> 4, c = lane & 15;
-    const int64_t p0 = ((int64_t)blockIdx.x * NF_MLP_WAVES + wave) * (16 * NT);
-    if (p0 >= n_points) return;
-    f32x4* act4 = lds + wave * (16 * NT * 64);
-    const int64_t n = n_points;
-    const NfW Wi = nf_w_image(packed_t, Net::PACKED_T);
-    auto sec = [&](int zs, int width) { return nf_slab_copy(dz, zs, width, p0, n); };
-    auto masks = [&](int l, uint2 (&m)[NT]) {
-#pragma unroll
-        for (int t = 0; t < NT; ++t)
-            m[t] = p0 + 16 * t < n ? *nf_mask_ptr<Net::S_MASK>(const_cast<float*>(saved), n, l, (p0 >> 4) + t, lane) : make_uint2(0u, 0u);
-    };
-    f32x4 frag_rgb[NT][1], frag_sig[NT];
-#pragma unroll
-    for (int t = 0; t < NT; ++t) {
-        const int64_t p = p0 + 16 * t + c;
-        f32x4 d = (f32x4){0.f, 0.f, 0.f, 0.f};
-        if (p < n && g == 0) d = reinterpret_cast<const f32x4*>(d_raw)[p];
-        frag_rgb[t][0] = (f32x4){d.x, d.y, d.z, 0.f};
-        frag_sig[t] = (f32x4){d.w, 0.f, 0.f, 0.f};
-    }
-    f32x4 acc[NT][16];
-    NfStream<NT> st;
-    f32x4 bj[NT];
-    uint64_t unused64[NT];
-    uint2 m[NT];
-#pragma unroll
-    for (int no = 0; no < 16; ++no) st.bias[no] = (f32x4){0.f, 0.f, 0.f, 0.f};      // C = 0: the C operand of every layer's first MFMAs
-    // d(layers_dir.2 out) = d rgb . fc_rgb.weight, masked by layers_dir.2's ReLU: one register chunk
-    masks(NX + 2, m);
-    nf_zero_acc<NT, 8>(acc);
-    nf_mma_from_regs<NT, 8, 1>(acc, reinterpret_cast<const f32x4*>(packed_t) + Net::OFFT_RGB / 4, frag_rgb, lane);
-    nf_apply_mask<NT, 8>(acc, m);
-    nf_store_act<NT, 8, false>(acc, act4, lane);
-    nf_load_w16<8>(st.wa, Wi, Net::OFFT_D2 / 4, lane);
-    nf_read_b<NT>(st.b0, act4, lane, 0);
-    // one layer from the slab: the slab = dZ section ZSEC_ (W4_ float4 per row) is copied out and consumed; the output is masked by
-    // ReLU layer MASKL_ under the last chunk and becomes the next slab
-#define NF_CHAIN_LAYER(OFF_, NO_, NCH_, W4_, ZSEC_, MASKL_, OFF_NEXT_, NO_NEXT_)                                       \
-    do {                                                                                                             \
-        NfCopyH<W4_, 4, false> cs{act4, sec(ZSEC_, 4 * (W4_)), lane, (NCH_) / 2, {}};                                  \
-        cs.prime();                                                                                                  \
-        masks(MASKL_, m);                                                                                            \
-        nf_seg_lds<NT, NO_, true, false, false>(acc, st, Wi, OFF_, NCH_, act4, lane, cs, unused64);                  \
-        nf_pending_b<NT, false>(bj, st);                                                                             \
-        nf_tail_dz<NT, NO_, NO_NEXT_, true>(acc, st.wb, bj, st, Wi, OFF_NEXT_, act4, lane, m);                       \
-    } while (0)
-    NF_CHAIN_LAYER(Net::OFFT_D2 / 4, 8, 8, 32, Net::Z_D2, NX + 1, Net::OFFT_D1 / 4, 8);
-    NF_CHAIN_LAYER(Net::OFFT_D1 / 4, 8, 8, 32, Net::Z_D1, NX, Net::OFFT_D0 / 4, 16);
+    // d(layers_dir.2 out) = d rgb . fc_rgb.weight, masked by layers_dir.2's ReLU
+    NF_NET_CHAIN_BEGIN(NX + 2, Net::OFFT_D2 / 4, 8);
+    NF_NET_CHAIN_LAYER(Net::OFFT_D2 / 4, 8, 8, 32, Net::Z_D2, NX + 1, Net::OFFT_D1 / 4, 8);
+    NF_NET_CHAIN_LAYER(Net::OFFT_D1 / 4, 8, 8, 32, Net::Z_D1, NX, Net::OFFT_D0 / 4, 16);
     // d feat = dZ_D0 . layers_dir.0.weight[:, :256] + d sigma * fc_alpha.weight   (no activation on feat): 8 slab chunks + one register chunk
     {
         f32x4 wd[16];
@@ -101,21 +52,16 @@ __device__ __forceinline__ void nf_paper_net_bwd_chain(f32x4* lds, const float* 
         nf_tail_dz<NT, 16, 16, false>(acc, wd, frag_sig, st, Wi, Net::OFFT_FEAT / 4, act4, lane, m);
     }
     if constexpr (Net::HAS_L5) {
-        NF_CHAIN_LAYER(Net::OFFT_FEAT / 4, 16, 16, 64, Net::Z_FEAT, 5, Net::OFFT_L5 / 4, 16);
-        NF_CHAIN_LAYER(Net::OFFT_L5 / 4, 16, 16, 64, Net::Z_L5, 4, Net::OFFT_L4 / 4, 16);
+        NF_NET_CHAIN_LAYER(Net::OFFT_FEAT / 4, 16, 16, 64, Net::Z_FEAT, 5, Net::OFFT_L5 / 4, 16);
+        NF_NET_CHAIN_LAYER(Net::OFFT_L5 / 4, 16, 16, 64, Net::Z_L5, 4, Net::OFFT_L4 / 4, 16);
     } else {
-        NF_CHAIN_LAYER(Net::OFFT_FEAT / 4, 16, 16, 64, Net::Z_FEAT, 4, Net::OFFT_L4 / 4, 16);
+        NF_NET_CHAIN_LAYER(Net::OFFT_FEAT / 4, 16, 16, 64, Net::Z_FEAT, 4, Net::OFFT_L4 / 4, 16);
     }
-    NF_CHAIN_LAYER(Net::OFFT_L4 / 4, 16, 16, 64, Net::Z_L4, 3, Net::OFFT_L3 / 4, 16);
-    NF_CHAIN_LAYER(Net::OFFT_L3 / 4, 16, 16, 64, Net::Z_L3, 2, Net::OFFT_L2 / 4, 16);       // hidden columns of the skip layer only
-    NF_CHAIN_LAYER(Net::OFFT_L2 / 4, 16, 16, 64, Net::Z_L2, 1, Net::OFFT_L1 / 4, 16);
-    NF_CHAIN_LAYER(Net::OFFT_L1 / 4, 16, 16, 64, Net::Z_L1, 0, 0, 0);
-#undef NF_CHAIN_LAYER
-    {   // the last section has no K loop behind it
-        const NfSlabCopy cp = sec(Net::Z_L0, 256);
-#pragma unroll 4
-        for (int k = 0; k < 16 * NT; ++k) nf_copy_rows<64>(act4, cp, k, lane);
-    }
+    NF_NET_CHAIN_LAYER(Net::OFFT_L4 / 4, 16, 16, 64, Net::Z_L4, 3, Net::OFFT_L3 / 4, 16);
+    NF_NET_CHAIN_LAYER(Net::OFFT_L3 / 4, 16, 16, 64, Net::Z_L3, 2, Net::OFFT_L2 / 4, 16);       // hidden columns of the skip layer only
+    NF_NET_CHAIN_LAYER(Net::OFFT_L2 / 4, 16, 16, 64, Net::Z_L2, 1, Net::OFFT_L1 / 4, 16);
+    NF_NET_CHAIN_LAYER(Net::OFFT_L1 / 4, 16, 16, 64, Net::Z_L1, 0, 0, 0);
+    NF_NET_CHAIN_END(Net::Z_L0);
 }
 
 // `chain` = the family's k_*_mlp_bwd_chain*<NF_MLP_NT>

@@ -79,7 +79,7 @@ k_smaller_mlp_fwd(const float* __restrict__ packed, const float* __restrict__ co
     const float* cond = cond_ + opaque0;
     f32x4 pe[NT][4];
     f32x4 dirf[NT][1];
-    nf_paper_net_inputs<NT>(pe, dirf, p0, n_points, S, lane, ro, rd, rd_view, z);
+    nf_net_inputs<NT>(pe, dirf, p0, n_points, S, lane, ro, rd, rd_view, z);
     f32x4 acc[NT][16];
     float sigma_raw[NT];
     const NfW Wi = nf_w_image(W, PACKED), Ci = nf_w_image(cond, COND_FLOATS);
