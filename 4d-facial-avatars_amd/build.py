@@ -17,7 +17,9 @@ OUT = os.path.join(OUT_DIR, "libnerface_hip.so")
 SOURCES = ["nf_lib.hip", "nf_rays.hip", "nf_choice.hip", "nf_render.hip", "nf_render_bwd_full.hip", "nf_mlp.hip", "nf_mlp_bwd.hip", "nf_mlp_bf16.hip", "nf_mlp_f16.hip", "nf_mlp_f16x2.hip", "nf_mlp_f16_train.hip", "nf_mlp_f16_bwd.hip", "nf_mlp_f16_dw.hip", "nf_mlp_bf16_train.hip", "nf_mlp_bf16_bwd.hip", "nf_mlp_bf16_dw.hip", "nf_tiny.hip", "nf_flex.hip", "nf_mlp_lcode.hip", "nf_mlp_lcode_bwd.hip", "nf_mlp_lcode_bf16.hip", "nf_mlp_lcode_f16.hip", "nf_mlp_lcode_f16x2.hip", "nf_mlp_lcode_f16_train.hip", "nf_mlp_lcode_f16_bwd.hip", "nf_mlp_lcode_bf16_train.hip", "nf_mlp_lcode_bf16_bwd.hip", "nf_mlp_bshape.hip", "nf_mlp_cbshape.hip", "nf_mlp_smaller.hip", "nf_mlp_smaller_bwd.hip", "nf_pipeline.hip", "nf_mlp_encoded.hip", "nf_optim.hip", "nf_metrics.hip",
            # density-only inference forwards: one unit per kernel
            "nf_mlp_sigma.hip", "nf_mlp_sigma_bf16.hip", "nf_mlp_sigma_f16.hip", "nf_mlp_sigma_f16x2.hip", "nf_mlp_lcode_sigma.hip",
-           "nf_mlp_lcode_sigma_bf16.hip", "nf_mlp_lcode_sigma_f16.hip", "nf_mlp_lcode_sigma_f16x2.hip", "nf_mlp_smaller_sigma.hip"]
+           "nf_mlp_lcode_sigma_bf16.hip", "nf_mlp_lcode_sigma_f16.hip", "nf_mlp_lcode_sigma_f16x2.hip", "nf_mlp_smaller_sigma.hip",
+           # exact-f32 inference forward with the colour layers on live samples only
+           "nf_mlp_live.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-fvisibility=default",
          "-Wno-unused-result"]
 

@@ -203,6 +203,40 @@ static inline dim3 nf_paper_net_condition_grid() { return dim3((Net::COND_FLOATS
         NF_NET_PE_B(3); nf_chunk<NT, 16, false>(acc, w, bj, st.bias);                                             \
     } while (0)
 
+// The colour layers, layers_dir.0 to fc_rgb, as stream text (locals acc / st / bj / dirf / sigma_raw / D0 / NDIR): the end of
+// nf_paper_net_body, and what k_paper_mlp_fwd_live (nf_mlp_live.hip) runs on the rows it has gathered.  Entry: feat in the slab;
+// layers_dir.0's bias in st.bias, its first weight chunk in st.wa and its first B fragment, as stored, in st.b0 -- what fc_feat's
+// nf_tail leaves.  Leaves rgb_raw in acc[t][0].xyz and sigma_raw in sigma_raw[t].
+#define NF_NET_COLOUR()                                                                                                    \
+    /* ---- layers_dir.0 : [feat | dir slots] -> 128; tile 8 row 0 = fc_alpha(feat) (Q2) ---- */                            \
+    {                                                                                                                      \
+        f32x4 wd[16];                                                                                                      \
+        nf_load_w16<9>(wd, Wi, D0 + 16 * 9 * 64, lane);                     /* the first dir-slot chunk's weights, a layer ahead */ \
+        nf_seg_lds<NT, 9, true, false>(acc, st, Wi, D0, 16, act4, lane);                                                   \
+        nf_pending_b<NT, false>(bj, st);                                                                                   \
+        nf_chunk<NT, 9, false>(acc, st.wb, bj, st.bias);                                                                   \
+        if (NDIR == 2) {                                                                                                   \
+            nf_load_w16<9>(st.wb, Wi, D0 + 17 * 9 * 64, lane);                                                             \
+            _Pragma("unroll") for (int t = 0; t < NT; ++t) bj[t] = dirf[t][0];                                             \
+            nf_chunk<NT, 9, false>(acc, wd, bj, st.bias);                                                                  \
+        }                                                                                                                  \
+        _Pragma("unroll") for (int t = 0; t < NT; ++t) bj[t] = dirf[t][NDIR - 1];                                          \
+        if constexpr (NDIR == 2) nf_tail<NT, 9, 8, 8, 1>(acc, st.wb, bj, st, Wi, Net::OFF_D1 / 4, Ci, Net::B_D1, act4, lane); \
+        else nf_tail<NT, 9, 8, 8, 1>(acc, wd, bj, st, Wi, Net::OFF_D1 / 4, Ci, Net::B_D1, act4, lane);                      \
+        _Pragma("unroll") for (int t = 0; t < NT; ++t) sigma_raw[t] = acc[t][8].x;                                         \
+    }                                                                                                                      \
+    /* ---- layers_dir.1, .2 ---- */                                                                                       \
+    nf_seg_lds<NT, 8, true, true>(acc, st, Wi, Net::OFF_D1 / 4, 8, act4, lane);                                            \
+    nf_pending_b<NT, true>(bj, st);                                                                                        \
+    nf_tail<NT, 8, 8, 8, 1>(acc, st.wb, bj, st, Wi, Net::OFF_D2 / 4, Ci, Net::B_D2, act4, lane);                           \
+    nf_seg_lds<NT, 8, true, true>(acc, st, Wi, Net::OFF_D2 / 4, 8, act4, lane);                                            \
+    nf_pending_b<NT, true>(bj, st);                                                                                        \
+    nf_tail<NT, 8, 8, 1, 1>(acc, st.wb, bj, st, Wi, Net::OFF_RGB / 4, Ci, Net::B_RGB, act4, lane);                         \
+    /* ---- fc_rgb ---- */                                                                                                 \
+    nf_seg_lds<NT, 1, true, true>(acc, st, Wi, Net::OFF_RGB / 4, 8, act4, lane);                                           \
+    nf_pending_b<NT, true>(bj, st);                                                                                        \
+    nf_chunk<NT, 1, false>(acc, st.wb, bj, st.bias)
+
 // The network from layers_xyz.0 to fc_rgb on the inference schedule, shared by the ray-input kernels and the pre-encoded ones:
 // every layer ends in nf_tail (raw accumulators to the slab tile by tile under the last chunk's MFMAs, the next layer's bias, first
 // weights and first B fragment fetched), every layer starts with the bias as the C operand of its first MFMAs, the ReLU is applied
@@ -260,37 +294,7 @@ __device__ __forceinline__ void nf_paper_net_body(f32x4 (&acc)[NT][16], float (&
     }
     NF_NET_LAYER256(Net::OFF_FEAT / 4, true, D0, Net::B_D0, 9, 1);
 #undef NF_NET_LAYER256
-    // ---- layers_dir.0 : [feat | dir slots] -> 128; tile 8 row 0 = fc_alpha(feat) (Q2) -----------------------
-    {
-        f32x4 wd[16];
-        nf_load_w16<9>(wd, Wi, D0 + 16 * 9 * 64, lane);                     // the first dir-slot chunk's weights, a layer ahead
-        nf_seg_lds<NT, 9, true, false>(acc, st, Wi, D0, 16, act4, lane);
-        nf_pending_b<NT, false>(bj, st);
-        nf_chunk<NT, 9, false>(acc, st.wb, bj, st.bias);
-        if (NDIR == 2) {
-            nf_load_w16<9>(st.wb, Wi, D0 + 17 * 9 * 64, lane);
-#pragma unroll
-            for (int t = 0; t < NT; ++t) bj[t] = dirf[t][0];
-            nf_chunk<NT, 9, false>(acc, wd, bj, st.bias);
-        }
-#pragma unroll
-        for (int t = 0; t < NT; ++t) bj[t] = dirf[t][NDIR - 1];
-        if constexpr (NDIR == 2) nf_tail<NT, 9, 8, 8, 1>(acc, st.wb, bj, st, Wi, Net::OFF_D1 / 4, Ci, Net::B_D1, act4, lane);
-        else nf_tail<NT, 9, 8, 8, 1>(acc, wd, bj, st, Wi, Net::OFF_D1 / 4, Ci, Net::B_D1, act4, lane);
-#pragma unroll
-        for (int t = 0; t < NT; ++t) sigma_raw[t] = acc[t][8].x;
-    }
-    // ---- layers_dir.1, .2 -----------------------------------------------------------------------------------
-    nf_seg_lds<NT, 8, true, true>(acc, st, Wi, Net::OFF_D1 / 4, 8, act4, lane);
-    nf_pending_b<NT, true>(bj, st);
-    nf_tail<NT, 8, 8, 8, 1>(acc, st.wb, bj, st, Wi, Net::OFF_D2 / 4, Ci, Net::B_D2, act4, lane);
-    nf_seg_lds<NT, 8, true, true>(acc, st, Wi, Net::OFF_D2 / 4, 8, act4, lane);
-    nf_pending_b<NT, true>(bj, st);
-    nf_tail<NT, 8, 8, 1, 1>(acc, st.wb, bj, st, Wi, Net::OFF_RGB / 4, Ci, Net::B_RGB, act4, lane);
-    // ---- fc_rgb -------------------------------------------------------------------------------------------
-    nf_seg_lds<NT, 1, true, true>(acc, st, Wi, Net::OFF_RGB / 4, 8, act4, lane);
-    nf_pending_b<NT, true>(bj, st);
-    nf_chunk<NT, 1, false>(acc, st.wb, bj, st.bias);
+    NF_NET_COLOUR();
 }
 
 // The pre-encoded forward of one wave (model.forward(x87, ...); inference only, the hot path never materialises x): same body,

@@ -190,6 +190,9 @@ SIGMA_ENTRY_POINTS = tuple(f"{_prefix}_mlp_sigma{_suffix}" for _prefix in ("nf_p
                            for _suffix in ("", "_bf16", "_f16", "_f16x2")) + ("nf_smaller_mlp_sigma",)
 _PROTOTYPES.update({_name: _SIGMA_SIG for _name in SIGMA_ENTRY_POINTS})
 _PROTOTYPES["nf_volume_weights_fwd"] = (C.c_int, [_P, _P, _P, _P, _L, _I, _P, _P, _P, _P])
+# colour layers on live samples only (paper family, exact f32): mlp_fwd + (scratch, scratch_floats, max_workgroups)
+_PROTOTYPES["nf_paper_mlp_fwd_live_scratch_floats"] = (_Z, [_I])
+_PROTOTYPES["nf_paper_mlp_fwd_live"] = (C.c_int, [_P, _P, _P, _P, _P, _P, _L, _I, _P, _P, _Z, _I, _P])
 for _prefix in ("nf_lcode", "nf_bshape", "nf_cbshape"):          # measurement hook (tools/time_blendshape.py)
     _PROTOTYPES[f"{_prefix}_mlp_bwd_stage_ms"] = (C.c_int, [_P, _P, _I, _P, _P, _P, _L, _I, _P, _Z, _P, _P, _P])
 # entry points that later ABI revisions add; absent symbols only fail when called

@@ -32,12 +32,18 @@ class _FusedNeRFModel(torch.nn.Module):
             hw = self._hip_weights = ops.MLPWeights(self.FAMILY, params)
         return hw
 
-    def hip_forward(self, ro, rd, z, rd_view, expr, latent, near, far, need_grad):
+    def hip_forward(self, ro, rd, z, rd_view, expr, latent, near, far, need_grad, live_only=False):
         """raw (R, S, 4) for the points ro + rd*z in the arithmetic of nerf.set_mlp_precision; `state` is what hip_backward needs
-        (None when no gradient is wanted)."""
+        (None when no gradient is wanted).  live_only: the colour of a sample without density, other than a ray's last, may come
+        back as 0.0 (ops.mlp_fwd_live) -- for a caller that integrates `raw` without noise; needs ops.live_colour_kernel(FAMILY)."""
         ops.check_conditioning(expr, latent)
         fam, hw, prec = self.FAMILY, self.hip_weights(), ops.get_mlp_precision()
         fam.require_precision(prec)
+        if live_only:
+            if need_grad or not ops.live_colour_kernel(fam):
+                raise ValueError("live_only is an exact-f32 inference option of the families in ops.LIVE_FAMILIES (ops.live_colour_kernel)")
+            packed = hw.get()
+            return ops.mlp_fwd_live(fam, packed, ops.mlp_condition(fam, packed, expr, latent, near, far), ro, rd, z, rd_view), None
         packed = hw.get()
         cond = ops.mlp_condition(fam, packed, expr, latent, near, far)
         if need_grad:

@@ -395,6 +395,59 @@ def mlp_fwd(fam: MLPFamily, precision: str, packed, cond, ro, rd, z, rd_view=Non
     return raw
 
 
+# Colour layers on live samples only (csrc/nf_mlp_live.hip): the exact-f32 inference forward of the families in LIVE_FAMILIES with
+# layers_dir.0 .. fc_rgb run only where the integrator can see the colour.  raw[..., 3] is mlp_fwd's everywhere, raw[..., :3] is
+# mlp_fwd's on live points (!(sigma <= 0), or the last sample of a ray) and 0.0 on the others -- so volume_render_fwd WITHOUT noise
+# gives the same outputs bit for bit, and that is the only caller it serves (_RenderChunk.forward).  Which passes of a render take the
+# kernel is a module switch: LIVE_PASSES_DEFAULT is what measured faster than the full kernel on whole frames (profiles/live_colour.md);
+# set_live_colour(True) turns it on for both passes, set_live_colour(False) off (A/B tests, tools/time_live_colour.py).
+# live_colour_launches() counts the launches of the kernel.
+LIVE_FAMILIES = ("nf_paper",)
+LIVE_PASSES_DEFAULT = ("coarse",)      # the fine pass does not gain (live fraction 0.74 .. 0.88): profiles/live_colour.md
+_live_passes = set(LIVE_PASSES_DEFAULT)
+_live_launches = [0]
+_LIVE_SCRATCH = {}                      # (device, stream, max_workgroups) -> the waves' rings of gathered rows
+
+
+def set_live_colour(on, passes=("coarse", "fine")) -> None:
+    """on=True: the passes named take the kernel; on=False: none does; on=None: back to LIVE_PASSES_DEFAULT."""
+    global _live_passes
+    _live_passes = set(LIVE_PASSES_DEFAULT) if on is None else (set(passes) if on else set())
+
+
+def live_colour_kernel(fam: MLPFamily) -> bool:
+    """The arithmetic is exact f32 and `fam` has the kernel."""
+    return _mlp_precision == "f32" and fam.prefix in LIVE_FAMILIES
+
+
+def live_colour_applies(fam: MLPFamily, which: str) -> bool:
+    """Pass `which` ("coarse" / "fine") of a render without noise takes the kernel: switched on for it, and live_colour_kernel."""
+    return which in _live_passes and live_colour_kernel(fam)
+
+
+def live_colour_launches() -> int:
+    return _live_launches[0]
+
+
+def mlp_fwd_live(fam: MLPFamily, packed, cond, ro, rd, z, rd_view=None, max_workgroups: int = 0) -> torch.Tensor:
+    """mlp_fwd(fam, "f32", ...) with zero colour on the dead points (see above) -> raw (n_rays, n_samples, 4).  max_workgroups > 0
+    caps the persistent grid (tests: a wave then walks many blocks and its ring wraps)."""
+    if fam.prefix not in LIVE_FAMILIES:
+        raise NotImplementedError(f"the {fam.prefix} model family has no live-colour kernel")
+    dev = H.require_device(packed, cond, ro, rd, z, rd_view)
+    n_rays, n_samples = z.shape
+    raw = torch.empty((n_rays, n_samples, 4), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        key = (dev, H.stream_ptr(dev), int(max_workgroups))
+        scratch = _LIVE_SCRATCH.get(key)
+        if scratch is None:
+            scratch = _LIVE_SCRATCH[key] = torch.empty(fam.fn("mlp_fwd_live_scratch_floats")(int(max_workgroups)), dtype=torch.float32, device=dev)
+        fam.call("mlp_fwd_live", H.ptr(packed), H.ptr(cond), H.ptr(ro), H.ptr(rd), H.ptr(rd_view), H.ptr(z), n_rays, n_samples, H.ptr(raw),
+                 H.ptr(scratch), scratch.numel(), int(max_workgroups), H.stream_ptr(dev))
+    _live_launches[0] += 1
+    return raw
+
+
 _SIGMA_ENTRY = {"f32": "mlp_sigma", "bf16x3": "mlp_sigma_bf16", "f16x3": "mlp_sigma_f16", "f16x2": "mlp_sigma_f16x2"}
 
 

@@ -79,6 +79,10 @@ class _RenderChunk(torch.autograd.Function):
         n_rays = ro.shape[0]
 
         lat_d = latent.detach().reshape(-1).contiguous()
+        # a pass integrated without noise never sees the colour of a sample without density (alpha = 0 exactly): the exact-f32
+        # inference kernel that skips the colour layers there serves it (ops.mlp_fwd_live); every other pass takes the full forward
+        live_c = not need_grad and noise_c is None and ops.live_colour_applies(model_c.FAMILY, "coarse")
+        live_f = not need_grad and noise_f is None and model_f is not None and ops.live_colour_applies(model_f.FAMILY, "fine")
         z_c = ops.sample_coarse(n_rays, nc, near, far, dev, t_rand, lindisp=cfg["lindisp"])
         if cfg.get("coarse_density_only"):
             # colour-free coarse pass (inference with a fine network): the coarse weights, disparity and acc depend on the density
@@ -86,13 +90,13 @@ class _RenderChunk(torch.autograd.Function):
             raw_c = state_c = rgb_c = None
             disp_c, acc_c, w_c = ops.volume_weights_fwd(model_c.hip_sigma(ro, rd, z_c, expr, lat_d, near, far), z_c, rd, noise_c)
         else:
-            raw_c, state_c = model_c.hip_forward(ro, rd, z_c, rd_view, expr, lat_d, near, far, need_grad)
+            raw_c, state_c = model_c.hip_forward(ro, rd, z_c, rd_view, expr, lat_d, near, far, need_grad, live_only=live_c)
             rgb_c, disp_c, acc_c, w_c = ops.volume_render_fwd(raw_c, z_c, rd, noise_c, bg, white)
         outs = [rgb_c, disp_c, acc_c]
         ctx.has_fine = nf > 0 and model_f is not None
         if ctx.has_fine:
             z_f = ops.resample_merge(z_c, w_c, nf, u)
-            raw_f, state_f = model_f.hip_forward(ro, rd, z_f, rd_view, expr, lat_d, near, far, need_grad)
+            raw_f, state_f = model_f.hip_forward(ro, rd, z_f, rd_view, expr, lat_d, near, far, need_grad, live_only=live_f)
             rgb_f, disp_f, acc_f, w_f = ops.volume_render_fwd(raw_f, z_f, rd, noise_f, bg, white)
             w_last = w_f[:, -1].contiguous()
             outs += [rgb_f, disp_f, acc_f, w_last]

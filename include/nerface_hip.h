@@ -610,6 +610,20 @@ NF_DECLARE_MLP_SIGMA(nf_smaller)                                          /* exa
 int nf_volume_weights_fwd(const float* sigma, const float* z, const float* rd, const float* noise, int64_t n_rays, int n_samples,
                           float* disp, float* acc, float* weights, nf_stream_t stream);
 
+/* ---- colour on live samples only (ABI 5 still: these only add) ---------------------------------------------------------------
+ * nf_paper_mlp_fwd_live: nf_paper_mlp_fwd (exact f32, inference) with the colour layers run only on the samples the integrator can
+ * see.  A point is live when !(sigma_raw <= 0) or it is the last sample of its ray; raw[..., 3] is nf_paper_mlp_fwd's for every
+ * point, raw[..., 0:3] is nf_paper_mlp_fwd's for every live point and 0.0 for every other one, bit for bit.  nf_volume_render_fwd
+ * WITHOUT a noise tensor gives the same outputs from either `raw` (alpha of a dead sample is exactly 0); with noise the ReLU
+ * argument is sigma_raw + noise, and the full forward is the one to call.
+ * scratch: nf_paper_mlp_fwd_live_scratch_floats(max_workgroups) floats, 16-byte aligned, contents irrelevant before and after the
+ * call (each wave's ring of gathered rows); one buffer serves the launches of one stream.  max_workgroups: 0 = the persistent grid of
+ * nf_paper_mlp_fwd (one workgroup per CU of the current device); > 0 caps it (a small launch then walks many blocks per wave).     */
+size_t nf_paper_mlp_fwd_live_scratch_floats(int max_workgroups);
+int nf_paper_mlp_fwd_live(const float* packed, const float* cond, const float* ro, const float* rd, const float* rd_view,
+                          const float* z, int64_t n_rays, int n_samples, float* raw, float* scratch, size_t scratch_floats,
+                          int max_workgroups, nf_stream_t stream);
+
 /* ---- host-only self-tests (no device needed): consistency of the weight-gradient job tables -- every slab entry written
  * exactly once per slice, tile ids inside their bundle.  0 = consistent, negative = which check failed.                 */
 int nf_selftest_dw_tables_f32(void);
