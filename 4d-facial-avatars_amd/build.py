@@ -19,7 +19,9 @@ SOURCES = ["nf_lib.hip", "nf_rays.hip", "nf_choice.hip", "nf_render.hip", "nf_re
            "nf_mlp_sigma.hip", "nf_mlp_sigma_bf16.hip", "nf_mlp_sigma_f16.hip", "nf_mlp_sigma_f16x2.hip", "nf_mlp_lcode_sigma.hip",
            "nf_mlp_lcode_sigma_bf16.hip", "nf_mlp_lcode_sigma_f16.hip", "nf_mlp_lcode_sigma_f16x2.hip", "nf_mlp_smaller_sigma.hip",
            # exact-f32 inference forward with the colour layers on live samples only
-           "nf_mlp_live.hip"]
+           "nf_mlp_live.hip",
+           # marching tetrahedra on a dense grid
+           "nf_isosurface.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-fvisibility=default",
          "-Wno-unused-result"]
 

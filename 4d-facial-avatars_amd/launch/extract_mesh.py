@@ -1,0 +1,110 @@
+"""Triangle mesh of a trained model's density surface for one test frame: the expression and latent code of frame I (picked as
+launch/eval_sharded.py picks them), the raw density on a dense grid (nerf.density_grid) and the surface of one level
+(ops.isosurface), written as .ply / .obj / .off.  Single rank.
+
+    python -m launch.extract_mesh --config cfg.yml --checkpoint ck --frame I --level L --resolution N [Ny Nz] --out mesh.ply \
+        [--bounds x0 y0 z0 x1 y1 z1] [--precision f32|f16x3|f16x2|bf16x3] [--coarse]
+
+Without --bounds the box is the axis-aligned hull of the frame's camera frustum between the config's near and far planes (the
+four image-corner rays of nerf.get_ray_bundle).  --level is in raw-density units (before the renderer's ReLU) and has no default.
+"""
+from __future__ import annotations
+
+import argparse
+import os
+
+import numpy as np
+import torch
+
+from . import common as CM
+from .common import nerf
+from nerf import ops
+
+
+def frustum_box(height: int, width: int, intrinsics, pose, near: float, far: float):
+    """(lo, hi): hull of the points o + d * near and o + d * far of the four image-corner rays."""
+    ro, rd = nerf.get_ray_bundle(height, width, intrinsics, pose)
+    o, d = (t[[0, 0, -1, -1], [0, -1, 0, -1]].double().cpu() for t in (ro, rd))
+    pts = torch.cat([o + d * near, o + d * far])
+    return pts.min(dim=0).values.tolist(), pts.max(dim=0).values.tolist()
+
+
+def main(argv=None):
+    keep = nerf.get_mlp_precision()          # the precision switch is process-global: leave it as the caller had it
+    try:
+        return _main(argv)
+    finally:
+        nerf.set_mlp_precision(keep)
+
+
+def _main(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--config", type=str, required=True)
+    ap.add_argument("--checkpoint", type=str, required=True)
+    ap.add_argument("--frame", type=int, required=True, help="test frame whose expression, latent code (and, without --bounds, camera) are used")
+    ap.add_argument("--level", type=float, required=True, help="raw density of the surface (before the renderer's ReLU)")
+    ap.add_argument("--resolution", type=int, nargs="+", required=True, metavar="N", help="grid points per axis: N, or Nx Ny Nz")
+    ap.add_argument("--out", type=str, required=True, help="mesh file: .ply (binary), .obj or .off")
+    ap.add_argument("--bounds", type=float, nargs=6, default=None, metavar=("X0", "Y0", "Z0", "X1", "Y1", "Z1"))
+    ap.add_argument("--precision", choices=["f32", "f16x3", "f16x2", "bf16x3"], default="f32")
+    ap.add_argument("--coarse", action="store_true", help="the coarse network's density (default: the fine network's, when the checkpoint has one)")
+    args = ap.parse_args(argv)
+    if len(args.resolution) not in (1, 3):
+        ap.error("--resolution takes one number or three")
+    if os.path.splitext(args.out)[1].lower() not in (".ply", ".obj", ".off"):
+        ap.error("--out: the extension names the format (.ply, .obj or .off)")
+    if not torch.cuda.is_available():
+        raise SystemExit("the MI355X `nerf` package needs a ROCm device")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    nerf.set_mlp_precision(args.precision)
+    cfg = CM.load_config(args.config)
+    _, poses, _, hwf, _, expressions, _, _ = nerf.load_flame_data(cfg.dataset.basedir, half_res=cfg.dataset.half_res,
+                                                                  testskip=cfg.dataset.testskip, test=True)
+    if not 0 <= args.frame < poses.shape[0]:
+        raise SystemExit(f"--frame {args.frame}: the test sequence has {poses.shape[0]} frames")
+    model_c, model_f = CM.build_models(cfg, dev)
+    ck = torch.load(args.checkpoint, map_location=dev)
+    model_c.load_state_dict(ck["model_coarse_state_dict"])
+    has_fine = bool(ck.get("model_fine_state_dict")) and model_f is not None
+    if has_fine:
+        model_f.load_state_dict(ck["model_fine_state_dict"])
+    model = model_c if args.coarse or not has_fine else model_f
+    model.eval()
+    H, W = int(ck.get("height", hwf[0])), int(ck.get("width", hwf[1]))
+    latent_codes = ck.get("latent_codes")
+    latent_codes = latent_codes.to(dev) if latent_codes is not None else torch.zeros(1, 32, device=dev)
+    row = 0
+    p = os.path.join(cfg.dataset.basedir, "index_map.npy")
+    if os.path.exists(p):
+        idx_map = np.load(p).astype(int)
+        row = int(idx_map[args.frame, 1]) if args.frame < len(idx_map) else 0
+    latent = latent_codes[min(max(row, 0), latent_codes.shape[0] - 1)]
+    expr = expressions[args.frame].float().to(dev)
+    if args.bounds is not None:
+        lo, hi = args.bounds[:3], args.bounds[3:]
+    else:
+        lo, hi = frustum_box(H, W, hwf[2], poses[args.frame, :3, :4].float().to(dev), float(cfg.dataset.near), float(cfg.dataset.far))
+    res = args.resolution * 3 if len(args.resolution) == 1 else args.resolution
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+    ev[0].record()
+    grid = nerf.density_grid(model, expr, latent, lo=lo, hi=hi, resolution=res)
+    ev[1].record()
+    mesh = nerf.Mesh(*ops.isosurface(grid, args.level, lo, hi, normals=True))
+    ev[2].record()
+    torch.cuda.synchronize()
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    nerf.write_mesh(args.out, mesh)
+    stats = {"lo": [float(x) for x in lo], "hi": [float(x) for x in hi], "resolution": [int(r) for r in res], "vertices": int(mesh.vertices.shape[0]),
+             "faces": int(mesh.faces.shape[0]), "density_s": ev[0].elapsed_time(ev[1]) * 1e-3, "extract_s": ev[1].elapsed_time(ev[2]) * 1e-3,
+             "network": "coarse" if model is model_c else "fine", "out": args.out}
+    print(f"frame {args.frame} ({stats['network']} network, {args.precision}): box lo {stats['lo']} hi {stats['hi']}, grid {stats['resolution']}, "
+          f"level {args.level}: V = {stats['vertices']}, F = {stats['faces']}; density {stats['density_s']:.4f} s, extraction {stats['extract_s']:.4f} s "
+          f"-> {args.out}")
+    if stats["faces"] == 0:
+        lo_v, hi_v = grid.min().item(), grid.max().item()
+        print(f"no surface at level {args.level}: the raw density on this grid spans [{lo_v:.4g}, {hi_v:.4g}]")
+    return stats
+
+
+if __name__ == "__main__":
+    main()

@@ -193,6 +193,11 @@ _PROTOTYPES["nf_volume_weights_fwd"] = (C.c_int, [_P, _P, _P, _P, _L, _I, _P, _P
 # colour layers on live samples only (paper family, exact f32): mlp_fwd + (scratch, scratch_floats, max_workgroups)
 _PROTOTYPES["nf_paper_mlp_fwd_live_scratch_floats"] = (_Z, [_I])
 _PROTOTYPES["nf_paper_mlp_fwd_live"] = (C.c_int, [_P, _P, _P, _P, _P, _P, _L, _I, _P, _P, _Z, _I, _P])
+# isosurface of a dense grid: count (workspace, V and F on the device), then emit (lo / hi are host float[3])
+_PROTOTYPES["nf_isosurface_workspace_bytes"] = (_Z, [_I, _I, _I])
+_PROTOTYPES["nf_isosurface_count"] = (C.c_int, [_P, _I, _I, _I, _F, _P, _Z, _P, _P])
+_PROTOTYPES["nf_isosurface_emit"] = (C.c_int, [_P, _I, _I, _I, _F, _P, _P, _P, _Z, _P, _L, _P, _L, _P, _P])
+_PROTOTYPES["nf_isosurface_table"] = (C.c_int, [_P])
 for _prefix in ("nf_lcode", "nf_bshape", "nf_cbshape"):          # measurement hook (tools/time_blendshape.py)
     _PROTOTYPES[f"{_prefix}_mlp_bwd_stage_ms"] = (C.c_int, [_P, _P, _I, _P, _P, _P, _L, _I, _P, _Z, _P, _P, _P])
 # entry points that later ABI revisions add; absent symbols only fail when called

@@ -1,0 +1,111 @@
+"""Geometry of a fused model: its raw density on a dense grid, the triangle mesh of one density level, and mesh files.
+
+    density_grid(model, expr, latent_code, lo=, hi=, resolution=)          -> (nz, ny, nx) raw density on the device
+    extract_mesh(model, expr, latent_code, lo=, hi=, resolution=, level=)  -> Mesh(vertices, faces, normals), device tensors
+    write_mesh(path, mesh)                                                 -> .off / .obj / .ply (binary little-endian), host code
+
+The density comes from the density-only kernels (nerf.density), the surface from ops.isosurface (csrc/nf_isosurface.hip).
+"""
+from __future__ import annotations
+
+import os
+from typing import NamedTuple, Optional
+
+import numpy as np
+import torch
+
+from . import ops
+from .models import density
+
+
+class Mesh(NamedTuple):
+    vertices: torch.Tensor                       # (V, 3) float32
+    faces: torch.Tensor                          # (F, 3) int32, counter-clockwise seen from outside (lower density)
+    normals: Optional[torch.Tensor]              # (V, 3) float32 unit vectors towards lower density, or None
+
+
+def _resolution(resolution):
+    r = [int(resolution)] * 3 if np.isscalar(resolution) else [int(x) for x in resolution]
+    if len(r) == 1:
+        r = r * 3
+    if len(r) != 3 or min(r) < 2:
+        raise ValueError(f"resolution: one number or (nx, ny, nz), at least 2 points per axis, got {resolution}")
+    return r
+
+
+def grid_axes(lo, hi, resolution):
+    """The coordinates of the grid points per axis, float32: lo + i * h with h = (hi - lo) / (n - 1), multiply then add -- the
+    positions ops.isosurface gives the same grid points."""
+    lo32, hi32 = ops._box(lo, hi, "density_grid")
+    return [lo32[a] + np.arange(n, dtype=np.float32) * ((hi32[a] - lo32[a]) / np.float32(n - 1)) for a, n in enumerate(_resolution(resolution))]
+
+
+def density_grid(model, expr, latent_code=None, *, lo, hi, resolution, chunk_points: int = 1 << 22):
+    """Raw density (nz, ny, nx) of a fused model on the grid of `resolution` (one number or (nx, ny, nz)) points spanning the box
+    [lo, hi], x fastest, for one expression (and latent code), in the arithmetic of nerf.set_mlp_precision.  Evaluated through
+    nerf.density in slabs of whole z planes of at most `chunk_points` points (at least one plane), so it carries that function's
+    guards and equals it bit for bit on the same points.  Runs under torch.no_grad()."""
+    if not (torch.is_tensor(expr) and expr.is_cuda):
+        raise RuntimeError("nerf (MI355X build): tensors must live on a ROCm device (`device='cuda'`); there is no CPU path in this package")
+    nx, ny, nz = _resolution(resolution)
+    dev = expr.device
+    xs, ys, zs = (torch.from_numpy(a).to(dev) for a in grid_axes(lo, hi, (nx, ny, nz)))
+    planes = max(1, int(chunk_points) // (nx * ny))
+    out = torch.empty((nz, ny, nx), dtype=torch.float32, device=dev)
+    with torch.no_grad():
+        for k0 in range(0, nz, planes):
+            k1 = min(nz, k0 + planes)
+            shape = (k1 - k0, ny, nx)
+            pts = torch.stack([xs.view(1, 1, nx).expand(shape), ys.view(1, ny, 1).expand(shape), zs[k0:k1].view(-1, 1, 1).expand(shape)], dim=-1)
+            out[k0:k1] = density(model, pts.reshape(-1, 3), expr, latent_code).view(shape)
+    return out
+
+
+def extract_mesh(model, expr, latent_code=None, *, lo, hi, resolution, level, normals: bool = True, chunk_points: int = 1 << 22) -> Mesh:
+    """The surface raw density == level of a fused model inside the box [lo, hi] for one expression (and latent code): density_grid,
+    then ops.isosurface.  `level` is in raw-density units (before the ReLU of the volume renderer) and has no default: what counts
+    as surface depends on the scene's scale and on how the model was trained."""
+    grid = density_grid(model, expr, latent_code, lo=lo, hi=hi, resolution=resolution, chunk_points=chunk_points)
+    return Mesh(*ops.isosurface(grid, float(level), lo, hi, normals=normals))
+
+
+def _host(mesh):
+    v, f, n = (tuple(mesh) + (None,))[:3]
+    to = lambda t, dt: None if t is None else np.ascontiguousarray((t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)), dtype=dt)
+    v, f, n = to(v, "<f4"), to(f, "<i4"), to(n, "<f4")
+    if v.ndim != 2 or v.shape[1] != 3 or f.ndim != 2 or f.shape[1] != 3 or (n is not None and n.shape != v.shape):
+        raise ValueError("write_mesh: expected vertices (V, 3), faces (F, 3) and normals (V, 3) or None")
+    return v, f, n
+
+
+def write_mesh(path: str, mesh) -> None:
+    """Write Mesh(vertices, faces, normals) -- or a (vertices, faces[, normals]) tuple -- in the format the extension names: .off
+    (positions and faces; floats printed with 9 significant digits, which round-trips float32), .obj (`vn` lines and `f a//a`
+    indices when there are normals) or .ply (binary little-endian: float x y z [nx ny nz], then uchar 3 + three int32 per face)."""
+    v, f, n = _host(mesh)
+    ext = os.path.splitext(path)[1].lower()
+    if ext == ".off":
+        with open(path, "w") as fh:
+            fh.write(f"OFF\n{len(v)} {len(f)} 0\n")
+            fh.writelines("%.9g %.9g %.9g\n" % tuple(p) for p in v.tolist())
+            fh.writelines("3 %d %d %d\n" % tuple(t) for t in f.tolist())
+    elif ext == ".obj":
+        with open(path, "w") as fh:
+            fh.writelines("v %.9g %.9g %.9g\n" % tuple(p) for p in v.tolist())
+            if n is not None:
+                fh.writelines("vn %.9g %.9g %.9g\n" % tuple(p) for p in n.tolist())
+                fh.writelines("f %d//%d %d//%d %d//%d\n" % (a, a, b, b, c, c) for a, b, c in (f + 1).tolist())
+            else:
+                fh.writelines("f %d %d %d\n" % tuple(t) for t in (f + 1).tolist())
+    elif ext == ".ply":
+        props = ["x", "y", "z"] + (["nx", "ny", "nz"] if n is not None else [])
+        header = "ply\nformat binary_little_endian 1.0\n" + f"element vertex {len(v)}\n" + "".join(f"property float {p}\n" for p in props) + \
+                 f"element face {len(f)}\nproperty list uchar int vertex_indices\nend_header\n"
+        rows = np.zeros(len(f), dtype=[("n", "u1"), ("i", "<i4", (3,))])
+        rows["n"], rows["i"] = 3, f
+        with open(path, "wb") as fh:
+            fh.write(header.encode("ascii"))
+            fh.write((v if n is None else np.concatenate([v, n], axis=1)).astype("<f4").tobytes())
+            fh.write(rows.tobytes())
+    else:
+        raise ValueError(f"write_mesh: unknown extension {ext!r} (.off, .obj or .ply)")

@@ -1083,3 +1083,50 @@ class ImageMetricsTable:
                 "nf_image_metrics")
         self.count = row + 1
         return row
+
+
+# ---------------------------------------------------------------------------------------- isosurface of a dense grid
+def _box(lo, hi, what: str):
+    lo, hi = [float(x) for x in lo], [float(x) for x in hi]
+    if len(lo) != 3 or len(hi) != 3:
+        raise ValueError(f"{what}: lo and hi are three numbers each")
+    lo32, hi32 = np.asarray(lo, dtype=np.float32), np.asarray(hi, dtype=np.float32)
+    if not bool(np.all(lo32 < hi32)):
+        raise ValueError(f"{what}: the box needs lo < hi on every axis (in float32), got lo={lo}, hi={hi}")
+    return lo32, hi32
+
+
+def isosurface(grid: torch.Tensor, level: float, lo, hi, normals: bool = False):
+    """Triangle mesh of the surface grid == level inside the box [lo, hi]: grid (nz, ny, nx) float32 on a ROCm device, x fastest,
+    grid point (i, j, k) at lo + (i, j, k) * (hi - lo) / (n - 1); a point is inside iff grid > level.  Marching tetrahedra on the
+    Kuhn triangulation (DESIGN.md "Isosurface"): welded vertices, consistent orientation (normals from inside to outside),
+    watertight wherever the box does not cut the surface, and the same bits from run to run.  Returns device tensors
+    (vertices (V, 3) float32, faces (F, 3) int32, normals (V, 3) float32 or None); an all-inside or all-outside grid gives (0, 3)
+    tensors.  Exactly one host read: the two counts, which size the outputs."""
+    if not torch.is_tensor(grid) or grid.dim() != 3:
+        raise ValueError("isosurface: expected a grid of shape (nz, ny, nx)")
+    grid = grid.detach().contiguous()
+    dev = H.require_device(grid)
+    nz, ny, nx = (int(s) for s in grid.shape)
+    if min(nx, ny, nz) < 2:
+        raise ValueError(f"isosurface: every axis needs at least 2 grid points, got (nz, ny, nx) = {(nz, ny, nx)}")
+    lo32, hi32 = _box(lo, hi, "isosurface")
+    lib = H.lib()
+    ws_bytes = int(lib.nf_isosurface_workspace_bytes(nx, ny, nz))
+    if ws_bytes == 0:
+        raise ValueError(f"isosurface: a grid of {nx} x {ny} x {nz} points is past the plan of csrc/nf_isosurface.hip (7 * points and "
+                         "12 * cells stay below 2^31: vertex and face ids are int32)")
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    counts = torch.empty(2, dtype=torch.int64, device=dev)
+    c_lo, c_hi = (C.c_float * 3)(*lo32.tolist()), (C.c_float * 3)(*hi32.tolist())
+    with torch.cuda.device(dev):
+        H.check(lib.nf_isosurface_count(H.ptr(grid), nx, ny, nz, float(level), H.ptr(ws), ws_bytes, H.ptr(counts), H.stream_ptr(dev)),
+                "nf_isosurface_count")
+        n_verts, n_faces = counts.tolist()                              # the one host read
+        verts = torch.empty((n_verts, 3), dtype=torch.float32, device=dev)
+        faces = torch.empty((n_faces, 3), dtype=torch.int32, device=dev)
+        norm = torch.empty((n_verts, 3), dtype=torch.float32, device=dev) if normals else None
+        if n_verts and n_faces:
+            H.check(lib.nf_isosurface_emit(H.ptr(grid), nx, ny, nz, float(level), C.addressof(c_lo), C.addressof(c_hi), H.ptr(ws), ws_bytes,
+                                           H.ptr(verts), n_verts, H.ptr(faces), n_faces, H.ptr(norm), H.stream_ptr(dev)), "nf_isosurface_emit")
+    return verts, faces, norm

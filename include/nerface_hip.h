@@ -624,6 +624,28 @@ int nf_paper_mlp_fwd_live(const float* packed, const float* cond, const float* r
                           const float* z, int64_t n_rays, int n_samples, float* raw, float* scratch, size_t scratch_floats,
                           int max_workgroups, nf_stream_t stream);
 
+/* ---- isosurface of a dense grid (ABI 5 still: these only add) ------------------------------------------------------------------
+ * grid: float32 [nz][ny][nx], x fastest; every axis n >= 2.  Marching tetrahedra on the Kuhn triangulation (DESIGN.md
+ * "Isosurface" is the specification): a welded, consistently oriented mesh, normals from inside (v > level) to outside; vertex ids
+ * in the order (k, j, i, owned edge), faces in the order (cell, tetrahedron, triangle); bit-identical from run to run (no atomics).
+ * nf_isosurface_count fills `workspace` (nf_isosurface_workspace_bytes(nx, ny, nz) bytes, 8-byte aligned; 0 = a size the plan
+ * does not serve: an axis below 2, or 7 * points or 12 * cells above 2^31 - 1, which bounds V and F before any launch) and writes
+ * counts_dev[0] = V, counts_dev[1] = F on the device.  nf_isosurface_emit, with the same grid, sizes, level and the workspace as
+ * that call left it, writes verts (V,3) f32, faces (F,3) i32 and, unless NULL, unit normals (V,3) f32 (the zero vector where the
+ * interpolated gradient is zero or not finite).  n_verts / n_faces are the CAPACITIES of the output buffers in rows: no row at or
+ * past them is written (the counts live on the device, so a smaller capacity truncates instead of failing); lo, hi: HOST float[3].
+ * NF_EINVAL before any device call: NULL pointers (normals excepted), an unserved size, workspace_bytes too small, !(lo < hi) on an
+ * axis, a negative capacity.  nf_isosurface_table: host only, the derived case table [6 tetrahedra][16 inside masks] -- six 4-bit
+ * vertex codes (tet vertex lo | hi << 2: the edge lo-hi) from bit 0, the number of triangles in bits 24-25, the flip bit in bit 26
+ * (the stored order has the flip applied).                                                                                      */
+size_t nf_isosurface_workspace_bytes(int nx, int ny, int nz);
+int nf_isosurface_count(const float* grid, int nx, int ny, int nz, float level, void* workspace, size_t workspace_bytes,
+                        int64_t* counts_dev, nf_stream_t stream);
+int nf_isosurface_emit(const float* grid, int nx, int ny, int nz, float level, const float* lo, const float* hi, void* workspace,
+                       size_t workspace_bytes, float* verts, int64_t n_verts, int* faces, int64_t n_faces, float* normals,
+                       nf_stream_t stream);
+int nf_isosurface_table(uint32_t* out);
+
 /* ---- host-only self-tests (no device needed): consistency of the weight-gradient job tables -- every slab entry written
  * exactly once per slice, tile ids inside their bundle.  0 = consistent, negative = which check failed.                 */
 int nf_selftest_dw_tables_f32(void);
