@@ -207,24 +207,34 @@ static inline dim3 nf_paper_net_condition_grid() { return dim3((Net::COND_FLOATS
 // nf_paper_net_body, and what k_paper_mlp_fwd_live (nf_mlp_live.hip) runs on the rows it has gathered.  Entry: feat in the slab;
 // layers_dir.0's bias in st.bias, its first weight chunk in st.wa and its first B fragment, as stored, in st.b0 -- what fc_feat's
 // nf_tail leaves.  Leaves rgb_raw in acc[t][0].xyz and sigma_raw in sigma_raw[t].
-#define NF_NET_COLOUR()                                                                                                    \
+// NF_NET_COLOUR_D0: layers_dir.0 alone, with its first dir-slot chunk's weights already requested into WD_.  NO0_ output tiles are
+// computed -- 9: with tile 8, whose row 0 is fc_alpha(feat) and ends up in sigma_raw[t]; 8: without it, sigma_raw is left alone --
+// from a weight section whose chunks are WS0_ tiles long (the packed image: 9).  Output tiles are independent MFMA chains: tiles
+// 0 .. 7 come out the same either way.
+#define NF_NET_COLOUR_D0(NO0_, WS0_, WD_)                                                                                  \
     /* ---- layers_dir.0 : [feat | dir slots] -> 128; tile 8 row 0 = fc_alpha(feat) (Q2) ---- */                            \
+    {                                                                                                                      \
+        nf_seg_lds<NT, NO0_, true, false, WS0_>(acc, st, Wi, D0, 16, act4, lane);                                          \
+        nf_pending_b<NT, false>(bj, st);                                                                                   \
+        nf_chunk<NT, NO0_, false>(acc, st.wb, bj, st.bias);                                                                \
+        if (NDIR == 2) {                                                                                                   \
+            nf_load_w16<NO0_>(st.wb, Wi, D0 + 17 * (WS0_) * 64, lane);                                                     \
+            _Pragma("unroll") for (int t = 0; t < NT; ++t) bj[t] = dirf[t][0];                                             \
+            nf_chunk<NT, NO0_, false>(acc, WD_, bj, st.bias);                                                              \
+        }                                                                                                                  \
+        _Pragma("unroll") for (int t = 0; t < NT; ++t) bj[t] = dirf[t][NDIR - 1];                                          \
+        if constexpr (NDIR == 2) nf_tail<NT, NO0_, 8, 8, 1>(acc, st.wb, bj, st, Wi, Net::OFF_D1 / 4, Ci, Net::B_D1, act4, lane); \
+        else nf_tail<NT, NO0_, 8, 8, 1>(acc, WD_, bj, st, Wi, Net::OFF_D1 / 4, Ci, Net::B_D1, act4, lane);                  \
+        if constexpr ((NO0_) > 8) { _Pragma("unroll") for (int t = 0; t < NT; ++t) sigma_raw[t] = acc[t][8].x; }           \
+    }
+#define NF_NET_COLOUR()                                                                                                    \
     {                                                                                                                      \
         f32x4 wd[16];                                                                                                      \
         nf_load_w16<9>(wd, Wi, D0 + 16 * 9 * 64, lane);                     /* the first dir-slot chunk's weights, a layer ahead */ \
-        nf_seg_lds<NT, 9, true, false>(acc, st, Wi, D0, 16, act4, lane);                                                   \
-        nf_pending_b<NT, false>(bj, st);                                                                                   \
-        nf_chunk<NT, 9, false>(acc, st.wb, bj, st.bias);                                                                   \
-        if (NDIR == 2) {                                                                                                   \
-            nf_load_w16<9>(st.wb, Wi, D0 + 17 * 9 * 64, lane);                                                             \
-            _Pragma("unroll") for (int t = 0; t < NT; ++t) bj[t] = dirf[t][0];                                             \
-            nf_chunk<NT, 9, false>(acc, wd, bj, st.bias);                                                                  \
-        }                                                                                                                  \
-        _Pragma("unroll") for (int t = 0; t < NT; ++t) bj[t] = dirf[t][NDIR - 1];                                          \
-        if constexpr (NDIR == 2) nf_tail<NT, 9, 8, 8, 1>(acc, st.wb, bj, st, Wi, Net::OFF_D1 / 4, Ci, Net::B_D1, act4, lane); \
-        else nf_tail<NT, 9, 8, 8, 1>(acc, wd, bj, st, Wi, Net::OFF_D1 / 4, Ci, Net::B_D1, act4, lane);                      \
-        _Pragma("unroll") for (int t = 0; t < NT; ++t) sigma_raw[t] = acc[t][8].x;                                         \
+        NF_NET_COLOUR_D0(9, 9, wd);                                                                                        \
     }                                                                                                                      \
+    NF_NET_COLOUR_REST()
+#define NF_NET_COLOUR_REST()                                                                                               \
     /* ---- layers_dir.1, .2 ---- */                                                                                       \
     nf_seg_lds<NT, 8, true, true>(acc, st, Wi, Net::OFF_D1 / 4, 8, act4, lane);                                            \
     nf_pending_b<NT, true>(bj, st);                                                                                        \
@@ -244,10 +254,17 @@ static inline dim3 nf_paper_net_condition_grid() { return dim3((Net::COND_FLOATS
 // columns, weights OFF_D0E) follow layers_dir.0's 16 feat chunks.  Leaves rgb_raw in acc[t][0].xyz and sigma_raw in sigma_raw[t].
 // SIGMA: the density-only forward.  Behind fc_feat only fc_alpha runs -- tile 8 of layers_dir.0 over its 16 feat chunks, the same
 // MFMAs in the same order as the full layer issues for acc[t][8]; the direction chunk, whose alpha row is zero, and everything
-// behind the layer are neither fetched nor issued.  Leaves sigma_raw[t]; acc[t][0] is not a colour.
-template <class Net, int NT, int NDIR, bool SIGMA = false>
+// behind the layer are neither fetched nor issued.  Leaves sigma_raw[t]; acc[t][0] is not a colour.  While that tile runs alone the
+// other accumulator tiles are dead: `pre` (SIGMA only) may request what the caller wants next -- pre.wait() stands in front of
+// fc_alpha's weight loads, pre.loads() behind them (k_paper_mlp_fwd_live, nf_mlp_live.hip; NfNoPre: nothing).
+struct NfNoPre {
+    __device__ __forceinline__ void wait() const {}
+    __device__ __forceinline__ void loads(const NfW&, const NfW&, int) const {}
+};
+template <class Net, int NT, int NDIR, bool SIGMA = false, class Pre = NfNoPre>
 __device__ __forceinline__ void nf_paper_net_body(f32x4 (&acc)[NT][16], float (&sigma_raw)[NT], const f32x4 (&pe)[NT][4],
-                                                  const f32x4 (&dirf)[NT][NDIR], const NfW& Wi, const NfW& Ci, f32x4* act4, int lane) {
+                                                  const f32x4 (&dirf)[NT][NDIR], const NfW& Wi, const NfW& Ci, f32x4* act4, int lane,
+                                                  Pre pre = Pre()) {
     constexpr unsigned D0 = (NDIR == 1 ? Net::OFF_D0 : Net::OFF_D0E) / 4;
     NfStream<NT> st;
     f32x4 bj[NT];
@@ -272,8 +289,10 @@ __device__ __forceinline__ void nf_paper_net_body(f32x4 (&acc)[NT][16], float (&
         NF_NET_LAYER256(Net::OFF_FEAT / 4, true, D0 + 8 * 64, Net::B_D0 + 128, 1, 1);      // next: tile 8 alone, its bias fragment
         f32x4 w8[16];
         w8[0] = st.wa[0];
+        pre.wait();
 #pragma unroll
         for (int ch = 1; ch < 16; ++ch) w8[ch] = nf_load_w1(Wi, D0 + (9 * ch + 8) * 64, lane);
+        pre.loads(Wi, Ci, lane);
 #pragma unroll
         for (int ch = 0; ch < 16; ++ch) {
             if (ch == 0) {

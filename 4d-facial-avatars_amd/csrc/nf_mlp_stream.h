@@ -195,30 +195,32 @@ __device__ __forceinline__ void nf_half(f32x4 (&acc)[NT][16], const f32x4 (&w)[1
 
 // The first nch - 1 of nch slab chunks of a layer (nch even).  Entry: st.wa / st.b0 hold chunk 0 (the fragment as stored).  Exit:
 // chunk nch - 1 is pending in st.wb / st.b1 -- the caller runs it with nf_tail (the layer ends there) or nf_chunk, through nf_pending_b.
-template <int NT, int NO, bool FIRST, bool RELU_IN, bool MASK, class Side>
+// NO output tiles are computed; a chunk of the weight section is WS tiles long (WS > NO: the section's last tiles are left out).
+template <int NT, int NO, bool FIRST, bool RELU_IN, bool MASK, int WS = NO, class Side>
 __device__ __forceinline__ void nf_seg_lds(f32x4 (&acc)[NT][16], NfStream<NT>& st, const NfW& W, unsigned wsec, int nch, const f32x4* act4,
                                            int lane, Side& side, uint64_t (&m64)[NT]) {
+    static_assert(WS >= NO, "a chunk holds at least the tiles computed");
     if (MASK) {                                   // (the first loop iteration finds no parked fragment: all zero = no bits)
 #pragma unroll
         for (int t = 0; t < NT; ++t) st.bp[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
     }
     __builtin_amdgcn_sched_barrier(0);
-    nf_half<NT, NO, FIRST, RELU_IN, MASK, true, true>(acc, st.wa, st.b0, st.wb, st.b1, st.bias, W, wsec + NO * 64, act4, lane, 1, side, 0, m64, st.bp);
+    nf_half<NT, NO, FIRST, RELU_IN, MASK, true, true>(acc, st.wa, st.b0, st.wb, st.b1, st.bias, W, wsec + WS * 64, act4, lane, 1, side, 0, m64, st.bp);
 #pragma unroll 1
     for (int ni = 1; ni < nch - 1; ni += 2) {
         const int step = (ni + 1) >> 1;
-        nf_half<NT, NO, false, RELU_IN, MASK, true, false>(acc, st.wb, st.b1, st.wa, st.b0, st.bias, W, wsec + (ni + 1) * NO * 64, act4, lane, ni + 1, side,
+        nf_half<NT, NO, false, RELU_IN, MASK, true, false>(acc, st.wb, st.b1, st.wa, st.b0, st.bias, W, wsec + (ni + 1) * WS * 64, act4, lane, ni + 1, side,
                                                            step, m64, st.bp);
-        nf_half<NT, NO, false, RELU_IN, MASK, false, true>(acc, st.wa, st.b0, st.wb, st.b1, st.bias, W, wsec + (ni + 2) * NO * 64, act4, lane, ni + 2, side,
+        nf_half<NT, NO, false, RELU_IN, MASK, false, true>(acc, st.wa, st.b0, st.wb, st.b1, st.bias, W, wsec + (ni + 2) * WS * 64, act4, lane, ni + 2, side,
                                                            step, m64, st.bp);
     }
 }
-template <int NT, int NO, bool FIRST, bool RELU_IN>
+template <int NT, int NO, bool FIRST, bool RELU_IN, int WS = NO>
 __device__ __forceinline__ void nf_seg_lds(f32x4 (&acc)[NT][16], NfStream<NT>& st, const NfW& W, unsigned wsec, int nch, const f32x4* act4,
                                            int lane) {
     NfNoCopy none;
     uint64_t unused[NT];
-    nf_seg_lds<NT, NO, FIRST, RELU_IN, false>(acc, st, W, wsec, nch, act4, lane, none, unused);
+    nf_seg_lds<NT, NO, FIRST, RELU_IN, false, WS>(acc, st, W, wsec, nch, act4, lane, none, unused);
 }
 
 // the pending chunk's fragment as the MFMAs take it

@@ -399,14 +399,28 @@ def mlp_fwd(fam: MLPFamily, precision: str, packed, cond, ro, rd, z, rd_view=Non
 # layers_dir.0 .. fc_rgb run only where the integrator can see the colour.  raw[..., 3] is mlp_fwd's everywhere, raw[..., :3] is
 # mlp_fwd's on live points (!(sigma <= 0), or the last sample of a ray) and 0.0 on the others -- so volume_render_fwd WITHOUT noise
 # gives the same outputs bit for bit, and that is the only caller it serves (_RenderChunk.forward).  Which passes of a render take the
-# kernel is a module switch: LIVE_PASSES_DEFAULT is what measured faster than the full kernel on whole frames (profiles/live_colour.md);
+# kernel is a module switch: LIVE_PASSES_DEFAULT is what measured faster than the full kernel per launch and on whole frames
+# (profiles/live_colour_fill.md; before the holes were filled in place the fine pass did not gain: profiles/live_colour.md);
 # set_live_colour(True) turns it on for both passes, set_live_colour(False) off (A/B tests, tools/time_live_colour.py).
 # live_colour_launches() counts the launches of the kernel.
 LIVE_FAMILIES = ("nf_paper",)
-LIVE_PASSES_DEFAULT = ("coarse",)      # the fine pass does not gain (live fraction 0.74 .. 0.88): profiles/live_colour.md
+LIVE_PASSES_DEFAULT = ("coarse", "fine")   # fine pass (live fraction 0.74 .. 0.88): -1.2 ms of 85.4 ms per launch
 _live_passes = set(LIVE_PASSES_DEFAULT)
 _live_launches = [0]
 _LIVE_SCRATCH = {}                      # (device, stream, max_workgroups) -> the waves' rings of gathered rows
+# The kernel's schedule constants (csrc/nf_mlp_live.hip), stated once for the host model of the schedule (tests/live_schedule_ref.py):
+# a wave's ring in `scratch` has LIVE_RING_ROWS rows of LIVE_ROW_BYTES (feat 1 KiB + direction fragments 64 B + index and sigma 16 B),
+# four waves per workgroup -- mlp_fwd_live_scratch_floats(w) == w * 4 * LIVE_RING_ROWS * LIVE_ROW_BYTES // 4; at most 31 rows are in
+# use.  LIVE_PREFETCH_ROWS oldest rows are requested while fc_alpha's row runs; holes beyond that are loaded behind the ballot.
+LIVE_RING_ROWS = 64
+LIVE_ROW_BYTES = 1024 + 64 + 16
+LIVE_PREFETCH_ROWS = 8
+
+
+def live_rotation_step(workgroups: int) -> int:
+    """Pass k of workgroup b of G takes block k G + (b + k step) mod G."""
+    step = (workgroups * 5 // 13) | 1
+    return step if step < workgroups else 0
 
 
 def set_live_colour(on, passes=("coarse", "fine")) -> None:

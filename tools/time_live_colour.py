@@ -1,5 +1,6 @@
 """Time the exact-f32 live-colour kernel (k_paper_mlp_fwd_live) beside the full inference kernel -- same GPU, same process, same
-points.  Prints a markdown report (profiles/live_colour.md keeps one, with the whole-frame figures of bench.py beside it).
+points.  Prints a markdown report (profiles/live_colour_fill.md and profiles/live_colour.md keep them, with the whole-frame figures
+of bench.py beside them).  NERFACE_HIP_LIB selects another build of the library, e.g. one with -DNF_LIVE_PF=N.
 
     python tools/time_live_colour.py [--frames 2 3 4 5 6] [--repeats 9] [--out FILE]
 
