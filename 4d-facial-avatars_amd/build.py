@@ -20,6 +20,8 @@ SOURCES = ["nf_lib.hip", "nf_rays.hip", "nf_choice.hip", "nf_render.hip", "nf_re
            "nf_mlp_lcode_sigma_bf16.hip", "nf_mlp_lcode_sigma_f16.hip", "nf_mlp_lcode_sigma_f16x2.hip", "nf_mlp_smaller_sigma.hip",
            # exact-f32 inference forward with the colour layers on live samples only
            "nf_mlp_live.hip",
+           # the same kernel with a per-wave record of its schedule (an instrument: tests, profiles/live_dynamic.md)
+           "nf_mlp_live_stats.hip",
            # marching tetrahedra on a dense grid
            "nf_isosurface.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-fvisibility=default",
@@ -32,6 +34,10 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fP
 UNIT_FLAGS = {u: ["-fno-slp-vectorize"] for u in ("nf_mlp_f16.hip", "nf_mlp_f16x2.hip", "nf_mlp_f16_train.hip", "nf_mlp_lcode_f16.hip",
                                                   "nf_mlp_lcode_f16x2.hip", "nf_mlp_lcode_f16_train.hip", "nf_mlp_sigma_f16.hip",
                                                   "nf_mlp_sigma_f16x2.hip", "nf_mlp_lcode_sigma_f16.hip", "nf_mlp_lcode_sigma_f16x2.hip")}
+# The live-colour kernel takes its next unit of work with a one-lane atomicAdd whose result it reads a whole pass later.  The atomic
+# optimiser would rewrite that add for "any number of active lanes" and read the result back with v_readfirstlane on the spot: a wait
+# for the counter's round trip at the top of every pass.
+UNIT_FLAGS.update({u: ["-mllvm", "-amdgpu-atomic-optimizer-strategy=None"] for u in ("nf_mlp_live.hip", "nf_mlp_live_stats.hip")})
 
 
 def _hipcc() -> str:

@@ -6,7 +6,15 @@
 // zero in every output; only the last sample of a ray (1e-6 is added to its density) and a NaN density keep their colour visible.
 // Such a point is LIVE: !(sigma_raw <= 0) or p % S == S - 1.  Every other point is dead and gets rgb_raw = 0.
 //
-// Same persistent grid as k_paper_mlp_fwd (one workgroup per CU, four independent waves, 32 points per wave pass, no barrier).  A pass:
+// Same persistent grid as k_paper_mlp_fwd (one workgroup per CU, four independent waves, 32 points per wave pass, no barrier), but no
+// fixed share of the points per wave: the launch is cut into units of 32 consecutive points (unit u = points 32 u .. 32 u + 31), and a
+// wave takes its next unit from a counter in device memory -- lane 0's atomicAdd, requested at the top of a pass for the pass after
+// it, so that the round trip runs beside the trunk, and made a scalar with readfirstlane at the bottom.  How long a unit takes
+// depends on whether its pass ends in a colour run, that is on where the object is; with fixed shares the launch ended with the
+// wave whose share held the most runs (profiles/live_dynamic.md; tools/live_schedule_sim.py replays both orders).  A wave whose unit is
+// past the end flushes its ring and leaves.  The counter is the library's (nf_live_counter, nf_mlp_live_kernel.h): one per stream,
+// zeroed on the stream in front of every launch.  The kernel, its helpers and the launch stand in nf_mlp_live_kernel.h, shared
+// with the instantiation that records what each wave did (nf_mlp_live_stats.hip).  A pass:
 //   1. the trunk through fc_feat and fc_alpha alone (nf_paper_net_body<..., SIGMA>): feat of the 32 points in the wave's LDS slab,
 //      sigma_raw in registers.  The pass has L live rows, D = 32 - L holes (dead or out-of-range points), and the wave's ring in
 //      `scratch` (global memory) holds R rows from earlier passes, R <= 31;
@@ -15,7 +23,7 @@
 //      point index, direction fragment and sigma_raw from the ring.  (r, g, b, sigma_raw) go to `raw` by point index;
 //   3. R < D (R + L <= 31): the L live rows are appended to the ring -- feat (1 KiB), the direction fragments (64 B), the point index
 //      and sigma_raw -- and no colour layer runs.
-// Dead points get (0, 0, 0, sigma_raw) in either case.  After its last block a wave runs the colour layers on what the ring holds,
+// Dead points get (0, 0, 0, sigma_raw) in either case.  After its last unit a wave runs the colour layers on what the ring holds,
 // moved into rows 0 .. R - 1 of the slab; the other rows hold whatever the slab held: MFMA columns are independent per point, and only
 // the valid ones are stored.  Every point of `raw` is written exactly once.  An all-live pass touches no ring memory.
 //
@@ -34,288 +42,7 @@
 // they are served by that L2, where the write-through stores of this CU have landed, never by a line the per-CU vector cache kept from
 // an earlier lap of the ring.  All ring traffic goes through a buffer descriptor that covers exactly the wave's ring: an index outside
 // it is dropped by the range check, not written (NF_LIVE_OOB makes use of that for the lanes and rows that have nothing to move).
-#include "nf_mlp_paper_net.h"
-
-#define NF_LIVE_ROWS 64                                   // ring rows per wave (at most 31 are in use at a time)
-#ifndef NF_LIVE_PF                                        // (a build flag for measuring other depths: profiles/live_colour_fill.md)
-#define NF_LIVE_PF 8                                      // ring rows requested while fc_alpha's row runs
-#endif
-#define NF_LIVE_DIR_B (NF_LIVE_ROWS * 1024)               // byte offsets inside a wave's ring: [rows][64] feat fragments, then
-#define NF_LIVE_META_B (NF_LIVE_DIR_B + NF_LIVE_ROWS * 64)     // [rows][4] direction fragments, then [rows] (index lo, hi, sigma_raw, -)
-#define NF_LIVE_WAVE_B (NF_LIVE_META_B + NF_LIVE_ROWS * 16)
-#define NF_LIVE_OOB NF_LIVE_WAVE_B                        // an offset the descriptor's range check drops (loads return 0)
-#define NF_LIVE_SC1 16                                    // cache policy bit of the buffer loads: sc1
-
-static_assert(NF_LIVE_ROWS == 64 && NF_MLP_NT == 2, "row numbers wrap with & 63; a pass's liveness is one 32-bit mask");
-static_assert(NF_LIVE_PF >= 0 && NF_LIVE_PF <= 16, "prefetched rows live in registers beside fc_alpha's weights");
-
-// the wave's ring as a buffer descriptor; the base comes back from its VGPR pair as a scalar (a descriptor in vector registers would put
-// a waterfall loop around every access)
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t nf_live_ring(char* ring_v) {
-    const uint64_t a = (uint64_t)ring_v;
-    const uint64_t s = (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)a) |
-                       ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(a >> 32)) << 32);
-    return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<char*>(s), (short)0, NF_LIVE_WAVE_B, 0x00020000);
-}
-__device__ __forceinline__ void nf_live_store(__amdgpu_buffer_rsrc_t ring, int off_b, f32x4 v) {
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(nf_u32x4, v), ring, off_b, 0, 0);
-}
-__device__ __forceinline__ f32x4 nf_live_load(__amdgpu_buffer_rsrc_t ring, int off_b) {
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(ring, off_b, 0, NF_LIVE_SC1));
-}
-// lowest set bit of a wave-uniform mask, taken off it
-__device__ __forceinline__ int nf_live_pop(unsigned& m) {
-    const int r = __builtin_ctz(m);
-    m &= m - 1u;
-    return r;
-}
-// slab address of fragment `lane` of row `prow` as the ring stores it (fragment = feature / 4)
-__device__ __forceinline__ int nf_live_slab(int prow, int lane) { return nf_act_idx4(prow, lane); }
-
-// What a pass requests while fc_alpha's row runs alone (the hook of nf_paper_net_body<..., SIGMA>): layers_dir.0's bias, first weight
-// chunk and direction-chunk weights as a colour run finds them, and the oldest ring rows, lane l holding fragment l.  The ring's
-// state comes from its VGPR homes and goes back to scalars here: nothing scalar crosses the trunk.
-struct NfLivePre {
-    NfStream<NF_MLP_NT>& st;
-    f32x4 (&wd)[16];
-    f32x4 (&pf)[NF_LIVE_PF > 0 ? NF_LIVE_PF : 1];
-    char* ring_v;
-    int head_v, tail_v;
-    // every append of the earlier passes has been acknowledged by L2 before the first load below is issued
-    __device__ __forceinline__ void wait() const {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        __builtin_amdgcn_s_waitcnt(0x0F70);               // vmcnt(0)
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-    }
-    __device__ __forceinline__ void loads(const NfW& Wi, const NfW& Ci, int lane) {
-        using Net = NfPaperNet;
-        const __amdgpu_buffer_rsrc_t ring = nf_live_ring(ring_v);
-        const int tail = __builtin_amdgcn_readfirstlane(tail_v), cnt = __builtin_amdgcn_readfirstlane(head_v) - tail;
-#pragma unroll
-        for (int i = 0; i < NF_LIVE_PF; ++i)
-            pf[i] = nf_live_load(ring, i < cnt ? ((tail + i) & (NF_LIVE_ROWS - 1)) * 1024 + lane * 16 : NF_LIVE_OOB);
-        nf_load_bias<8>(st.bias, Ci, Net::B_D0, lane);
-        nf_load_w16<8>(st.wa, Wi, Net::OFF_D0 / 4, lane);
-        nf_load_w16<8>(wd, Wi, Net::OFF_D0 / 4 + 16 * 9 * 64, lane);
-        __builtin_amdgcn_sched_barrier(0);
-    }
-};
-
-template <int NT>
-__global__ void __launch_bounds__(64 * NF_MLP_WAVES, 1)
-k_paper_mlp_fwd_live(const float* __restrict__ packed, const float* __restrict__ cond_, const float* __restrict__ ro,
-                     const float* __restrict__ rd, const float* __restrict__ rd_view, const float* __restrict__ z,
-                     int64_t n_points, int S, float* __restrict__ raw, float* __restrict__ scratch) {
-    using Net = NfPaperNet;
-    __shared__ __attribute__((aligned(16))) f32x4 lds[NF_MLP_WAVES * 16 * NT * 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    f32x4* act4 = lds + wave * (16 * NT * 64);
-    typedef __attribute__((address_space(1))) f32x4 nf_gf32x4;
-    // loop invariants and the ring's fill state live in VGPRs, as in k_paper_mlp_fwd: the layer stream leaves no scalar registers
-    nf_gf32x4* raw_v = (nf_gf32x4*)raw;
-    asm volatile("" : "+v"(raw_v));
-    int stride_v = (int)gridDim.x;
-    asm volatile("" : "+v"(stride_v));
-    char* ring_v = reinterpret_cast<char*>(scratch) + ((size_t)blockIdx.x * NF_MLP_WAVES + wave) * NF_LIVE_WAVE_B;
-    asm volatile("" : "+v"(ring_v));
-    const float* z_v = z;
-    const float* rdv_v = rd_view;
-    asm volatile("" : "+v"(z_v), "+v"(rdv_v));
-    int head_v = 0, tail_v = 0;                           // rows appended / consumed so far (row = count & 63); head - tail <= 31
-    asm volatile("" : "+v"(head_v), "+v"(tail_v));
-    // Pass k of workgroup b takes block k G + (b + k R) mod G of the G = gridDim.x blocks of that pass, not block k G + b: with a fixed
-    // b a workgroup would see the same few image columns in every pass (a 65536 x 64 launch: G blocks = one image row), and the
-    // colour work, which depends on where the object is, would pile up on the workgroups of the columns that cross it.
-    int rot_v = (int)blockIdx.x, step_v = ((int)gridDim.x * 5 / 13) | 1;
-    if (step_v >= (int)gridDim.x) step_v = 0;             // (one workgroup)
-    asm volatile("" : "+v"(rot_v), "+v"(step_v));
-#pragma unroll 1
-    for (int64_t base = 0;; base += __builtin_amdgcn_readfirstlane(stride_v)) {
-        const int64_t blk = base + __builtin_amdgcn_readfirstlane(rot_v);
-        {
-            const int g_n = __builtin_amdgcn_readfirstlane(stride_v);
-            int r = __builtin_amdgcn_readfirstlane(rot_v) + __builtin_amdgcn_readfirstlane(step_v);
-            rot_v = r >= g_n ? r - g_n : r;
-            asm volatile("" : "+v"(rot_v));
-        }
-        const int64_t p0 = (blk * NF_MLP_WAVES + wave) * (16 * NT);
-        int64_t p0_v = p0;                                // (its home across the trunk and the colour run)
-        asm volatile("" : "+v"(p0_v));
-        int more_v = p0 < n_points;                       // wave-uniform; no barriers anywhere below
-        asm volatile("" : "+v"(more_v));
-        const bool more = __builtin_amdgcn_readfirstlane(more_v) != 0;
-        int opaque0 = 0;                                  // per-block opaque zero: the weight / bias loads must stay where the layers issue them
-        asm volatile("" : "+s"(opaque0));
-        const NfW Wi = nf_w_image(packed + opaque0, Net::PACKED), Ci = nf_w_image(cond_ + opaque0, Net::COND_FLOATS);
-        NfStream<NT> st;
-        f32x4 wd[16], pf[NF_LIVE_PF > 0 ? NF_LIVE_PF : 1];
-        f32x4 dirf[NT][1];
-        float sigma_own[NT];
-        int live_v = 0, run_v = 0;                        // the pass's 32-bit liveness mask; nonzero: the colour layers run
-        if (more) {
-            f32x4 pe[NT][4];
-            nf_net_inputs<NT>(pe, dirf, p0, n_points, S, lane, ro, rd, rdv_v, z_v);
-            f32x4 acc[NT][16];
-            nf_paper_net_body<Net, NT, 1, true>(acc, sigma_own, pe, dirf, Wi, Ci, act4, lane, NfLivePre{st, wd, pf, ring_v, head_v, tail_v});
-            int lane_o = lane;
-            asm volatile("" : "+v"(lane_o));
-            const int g = lane_o >> 4, c = lane_o & 15;
-            // lane group 0 holds sigma_raw of point 16 t + c: liveness as one 16-bit mask per tile
-            unsigned live = 0;
-            int S_o = S;                                  // (opaque: nothing derived from S is hoisted out of the block loop)
-            asm volatile("" : "+v"(S_o));
-            const int64_t p0_o = (int64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)p0_v) |
-                                 ((int64_t)__builtin_amdgcn_readfirstlane((int)(p0_v >> 32)) << 32);
-#pragma unroll
-            for (int t = 0; t < NT; ++t) {
-                const int64_t p = p0_o + 16 * t + c;
-                const bool is_live = g == 0 && p < n_points && (!(sigma_own[t] <= 0.0f) || (p + 1) % S_o == 0);
-                live |= ((unsigned)__builtin_amdgcn_ballot_w64(is_live) & 0xffffu) << (16 * t);
-            }
-            const int head = __builtin_amdgcn_readfirstlane(head_v), cnt = head - __builtin_amdgcn_readfirstlane(tail_v);
-            const int n_live = __builtin_popcount(live);
-            live_v = (int)live;
-            if (cnt + n_live >= 16 * NT) {                // the ring fills every hole
-                run_v = 1;
-            } else {                                      // append the live rows; nothing runs
-                const __amdgpu_buffer_rsrc_t ring = nf_live_ring(ring_v);
-                unsigned mm = live;
-#pragma unroll 1
-                for (int i = 0; i < n_live; i += 4) {
-                    f32x4 v[4];
-                    int off[4];
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) {
-                        const bool ok = i + u < n_live;
-                        const int r = ok ? nf_live_pop(mm) : 0;
-                        off[u] = ok ? ((head + i + u) & (NF_LIVE_ROWS - 1)) * 1024 + lane_o * 16 : NF_LIVE_OOB;
-                        v[u] = act4[nf_live_slab(r, lane_o)];
-                    }
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) nf_live_store(ring, off[u], v[u]);
-                }
-#pragma unroll
-                for (int t = 0; t < NT; ++t) {
-                    const int bit = 16 * t + c;
-                    if ((live >> bit) & 1u) {
-                        const int row = (head + __builtin_popcount(live & ((1u << bit) - 1u))) & (NF_LIVE_ROWS - 1);
-                        nf_live_store(ring, NF_LIVE_DIR_B + row * 64 + g * 16, dirf[t][0]);
-                        if (g == 0) {
-                            const int64_t p = p0_o + bit;
-                            nf_live_store(ring, NF_LIVE_META_B + row * 16,
-                                          (f32x4){__int_as_float((int)(uint32_t)p), __int_as_float((int)(p >> 32)), sigma_own[t], 0.0f});
-                        }
-                    }
-                }
-                head_v = head + n_live;
-                asm volatile("" : "+v"(head_v));
-            }
-        } else {
-            // behind the wave's last block: what the ring holds goes to rows 0 .. R - 1 of the slab.  (The requests are made with an
-            // empty ring too, once per wave: every path into the colour run below defines what it reads.)
-            NfLivePre pre{st, wd, pf, ring_v, head_v, tail_v};
-            pre.wait();
-            pre.loads(Wi, Ci, lane);
-#pragma unroll
-            for (int t = 0; t < NT; ++t) {
-                dirf[t][0] = (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
-                sigma_own[t] = 0.0f;
-            }
-            run_v = __builtin_amdgcn_readfirstlane(head_v) != __builtin_amdgcn_readfirstlane(tail_v) ? 2 : 0;
-        }
-        asm volatile("" : "+v"(live_v), "+v"(run_v));
-        const int run = __builtin_amdgcn_readfirstlane(run_v);
-        if (run != 0) {
-            int lane_o = lane;
-            asm volatile("" : "+v"(lane_o));
-            const int g = lane_o >> 4, c = lane_o & 15;
-            const __amdgpu_buffer_rsrc_t ring = nf_live_ring(ring_v);
-            const int tail = __builtin_amdgcn_readfirstlane(tail_v), cnt = __builtin_amdgcn_readfirstlane(head_v) - tail;
-            const unsigned own = run == 1 ? (unsigned)__builtin_amdgcn_readfirstlane(live_v) : 0u;      // rows that stay as they are
-            const unsigned fill = run == 1 ? ~own : (1u << cnt) - 1u;                                    // rows the ring fills, oldest first
-            const int n_fill = __builtin_popcount(fill);
-            // index, direction fragment and sigma_raw of a filled row, gathered per lane
-            f32x4 meta[NT];
-            bool valid[NT];
-#pragma unroll
-            for (int t = 0; t < NT; ++t) {
-                const int bit = 16 * t + c;
-                const bool f = (fill >> bit) & 1u;
-                const int row = (tail + __builtin_popcount(fill & ((1u << bit) - 1u))) & (NF_LIVE_ROWS - 1);
-                const f32x4 fd = nf_live_load(ring, f ? NF_LIVE_DIR_B + row * 64 + g * 16 : NF_LIVE_OOB);
-                const f32x4 fm = nf_live_load(ring, f ? NF_LIVE_META_B + row * 16 : NF_LIVE_OOB);
-                const int64_t p = (p0_v) + bit;
-                dirf[t][0] = f ? fd : dirf[t][0];
-                meta[t] = f ? fm : (f32x4){__int_as_float((int)(uint32_t)p), __int_as_float((int)(p >> 32)), sigma_own[t], 0.0f};
-                valid[t] = f || ((own >> bit) & 1u);
-            }
-            // the rows themselves: the prefetched ones from their registers, the others loaded here
-            unsigned hh = fill;
-#pragma unroll
-            for (int i = 0; i < NF_LIVE_PF; ++i) {
-                if (i < n_fill) {
-                    const int h = nf_live_pop(hh);
-                    act4[nf_live_slab(h, lane_o)] = pf[i];
-                }
-            }
-#pragma unroll 1
-            for (int i = NF_LIVE_PF; i < n_fill; i += 4) {
-                f32x4 v[4];
-                int h[4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const bool ok = i + u < n_fill;
-                    h[u] = ok ? nf_live_pop(hh) : -1;
-                    v[u] = nf_live_load(ring, ok ? ((tail + i + u) & (NF_LIVE_ROWS - 1)) * 1024 + lane_o * 16 : NF_LIVE_OOB);
-                }
-#pragma unroll
-                for (int u = 0; u < 4; ++u)
-                    if (h[u] >= 0) act4[nf_live_slab(h[u], lane_o)] = v[u];
-            }
-            // layers_dir.0 starts as a layer's tail would leave it: bias and first weight chunk requested (NfLivePre), first B fragment
-            // as stored.  Output tiles 0 .. 7 only; the weight image keeps its 9-tile chunk stride.
-            constexpr int NDIR = 1;
-            constexpr unsigned D0 = Net::OFF_D0 / 4;
-            nf_read_b<NT>(st.b0, act4, lane, 0);
-            f32x4 acc[NT][16], bj[NT];
-            float sigma_raw[NT];
-            NF_NET_COLOUR_D0(8, 9, wd);
-            NF_NET_COLOUR_REST();
-            int lane_s = lane;
-            asm volatile("" : "+v"(lane_s));
-            if ((lane_s >> 4) == 0) {
-#pragma unroll
-                for (int t = 0; t < NT; ++t) {
-                    if (valid[t]) {
-                        const int64_t p = (int64_t)(uint32_t)__float_as_int(meta[t].x) | ((int64_t)__float_as_int(meta[t].y) << 32);
-                        if (p >= 0 && p < n_points) raw_v[p] = (f32x4){acc[t][0].x, acc[t][0].y, acc[t][0].z, meta[t].z};
-                    }
-                }
-            }
-            tail_v = tail + n_fill;
-            asm volatile("" : "+v"(tail_v));
-        }
-        asm volatile("" : "+v"(more_v));
-        if (__builtin_amdgcn_readfirstlane(more_v) == 0) break;
-        {   // the dead points of the block: finished without a colour
-            int lane_s = lane;
-            asm volatile("" : "+v"(lane_s));
-            const int g = lane_s >> 4, c = lane_s & 15;
-            asm volatile("" : "+v"(live_v));
-#pragma unroll
-            for (int t = 0; t < NT; ++t) {
-                const int64_t p = p0_v + 16 * t + c;
-                if (g == 0 && p < n_points && !(((unsigned)live_v >> (16 * t + c)) & 1u)) raw_v[p] = (f32x4){0.0f, 0.0f, 0.0f, sigma_own[t]};
-            }
-        }
-    }
-}
-
-// floats of `scratch` for a grid capped at max_workgroups (0: one workgroup per CU of the current device)
-static int64_t nf_live_grid_cap(int max_workgroups) {
-    const int64_t cu = nf_cu_count();
-    return max_workgroups > 0 && max_workgroups < cu ? max_workgroups : cu;
-}
+#include "nf_mlp_live_kernel.h"
 
 extern "C" size_t nf_paper_mlp_fwd_live_scratch_floats(int max_workgroups) {
     return (size_t)nf_live_grid_cap(max_workgroups) * NF_MLP_WAVES * (NF_LIVE_WAVE_B / 4);
@@ -324,13 +51,5 @@ extern "C" size_t nf_paper_mlp_fwd_live_scratch_floats(int max_workgroups) {
 extern "C" int nf_paper_mlp_fwd_live(const float* packed, const float* cond, const float* ro, const float* rd, const float* rd_view,
                                      const float* z, int64_t n_rays, int n_samples, float* raw, float* scratch, size_t scratch_floats,
                                      int max_workgroups, nf_stream_t stream) {
-    static_assert(NF_MLP_WAVES * 16 * NF_MLP_NT == 128, "nf_mlp_fwd_launch sizes the grid for 128 points per workgroup");
-    if (max_workgroups < 0 || !scratch || ((uintptr_t)scratch & 15) || scratch_floats < nf_paper_mlp_fwd_live_scratch_floats(max_workgroups))
-        return NF_EINVAL;
-    const float* rdv = rd_view ? rd_view : rd;
-    return nf_mlp_fwd_launch(NF_FWD_INFER, packed, cond, ro, rd, z, raw, nullptr, n_rays, n_samples, [&](int64_t n_points, unsigned grid) {
-        const int64_t cap = nf_live_grid_cap(max_workgroups);
-        hipLaunchKernelGGL(k_paper_mlp_fwd_live<NF_MLP_NT>, dim3((unsigned)(grid < cap ? grid : cap)), dim3(64 * NF_MLP_WAVES), 0, nf_s(stream),
-                           packed, cond, ro, rd, rdv, z, n_points, n_samples, raw, scratch);
-    });
+    return nf_live_launch<false>(packed, cond, ro, rd, rd_view, z, n_rays, n_samples, raw, scratch, scratch_floats, max_workgroups, nullptr, stream);
 }

@@ -193,6 +193,8 @@ _PROTOTYPES["nf_volume_weights_fwd"] = (C.c_int, [_P, _P, _P, _P, _L, _I, _P, _P
 # colour layers on live samples only (paper family, exact f32): mlp_fwd + (scratch, scratch_floats, max_workgroups)
 _PROTOTYPES["nf_paper_mlp_fwd_live_scratch_floats"] = (_Z, [_I])
 _PROTOTYPES["nf_paper_mlp_fwd_live"] = (C.c_int, [_P, _P, _P, _P, _P, _P, _L, _I, _P, _P, _Z, _I, _P])
+# the same launch through the instantiation that records its schedule: + (stats, stats_rows) in front of the stream
+_PROTOTYPES["nf_paper_mlp_fwd_live_stats"] = (C.c_int, [_P, _P, _P, _P, _P, _P, _L, _I, _P, _P, _Z, _I, _P, _Z, _P])
 # isosurface of a dense grid: count (workspace, V and F on the device), then emit (lo / hi are host float[3])
 _PROTOTYPES["nf_isosurface_workspace_bytes"] = (_Z, [_I, _I, _I])
 _PROTOTYPES["nf_isosurface_count"] = (C.c_int, [_P, _I, _I, _I, _F, _P, _Z, _P, _P])

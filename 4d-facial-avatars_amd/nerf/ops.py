@@ -417,8 +417,10 @@ LIVE_ROW_BYTES = 1024 + 64 + 16
 LIVE_PREFETCH_ROWS = 8
 
 
+# The FORMER static order of the kernel, kept for the host model of that order (tests/live_schedule_ref.py): the kernel now hands out
+# 32-point units from a counter, in the order the waves come for them (tools/live_schedule_sim.py replays both).
 def live_rotation_step(workgroups: int) -> int:
-    """Pass k of workgroup b of G takes block k G + (b + k step) mod G."""
+    """Pass k of workgroup b of G took block k G + (b + k step) mod G."""
     step = (workgroups * 5 // 13) | 1
     return step if step < workgroups else 0
 
@@ -460,6 +462,28 @@ def mlp_fwd_live(fam: MLPFamily, packed, cond, ro, rd, z, rd_view=None, max_work
                  H.ptr(scratch), scratch.numel(), int(max_workgroups), H.stream_ptr(dev))
     _live_launches[0] += 1
     return raw
+
+
+LIVE_STAT_COLUMNS = ("units", "colour_runs", "flush_rows", "exit_clock")
+
+
+def mlp_fwd_live_stats(fam: MLPFamily, packed, cond, ro, rd, z, rd_view=None, max_workgroups: int = 0):
+    """mlp_fwd_live through the kernel's statistics instantiation (csrc/nf_mlp_live_stats.hip) -> (raw, stats): stats is int64
+    (waves, 4) in the order of LIVE_STAT_COLUMNS, one row per wave of the capped grid (workgroup * 4 + wave; rows of workgroups the
+    launch did not start stay zero); exit_clock is the device's wall_clock64() when the wave left.  An instrument for tests and
+    profiles (tools/live_schedule_sim.py); no render path calls it."""
+    if fam.prefix not in LIVE_FAMILIES:
+        raise NotImplementedError(f"the {fam.prefix} model family has no live-colour kernel")
+    dev = H.require_device(packed, cond, ro, rd, z, rd_view)
+    n_rays, n_samples = z.shape
+    raw = torch.empty((n_rays, n_samples, 4), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        scratch = torch.empty(fam.fn("mlp_fwd_live_scratch_floats")(int(max_workgroups)), dtype=torch.float32, device=dev)
+        waves = scratch.numel() * 4 // (LIVE_RING_ROWS * LIVE_ROW_BYTES)
+        stats = torch.empty((waves, len(LIVE_STAT_COLUMNS)), dtype=torch.int64, device=dev)
+        fam.call("mlp_fwd_live_stats", H.ptr(packed), H.ptr(cond), H.ptr(ro), H.ptr(rd), H.ptr(rd_view), H.ptr(z), n_rays, n_samples,
+                 H.ptr(raw), H.ptr(scratch), scratch.numel(), int(max_workgroups), stats.data_ptr(), waves, H.stream_ptr(dev))
+    return raw, stats
 
 
 _SIGMA_ENTRY = {"f32": "mlp_sigma", "bf16x3": "mlp_sigma_bf16", "f16x3": "mlp_sigma_f16", "f16x2": "mlp_sigma_f16x2"}

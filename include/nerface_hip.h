@@ -10,7 +10,8 @@
  * `stream` is a hipStream_t (NULL = default stream); kernels are enqueued asynchronously; the return
  * value is 0 on success or the hipError_t of the failed launch (nf_error_string() renders it), and
  * NF_EINVAL (-22) for an argument the library rejects.  No entry point allocates, frees or synchronises,
- * except nf_paper_pack's one-time upload of its (static) gather table.
+ * except nf_paper_pack's one-time upload of its (static) gather table and the first nf_paper_mlp_fwd_live
+ * on a device, which allocates that device's unit counters.
  */
 #ifndef NERFACE_HIP_H
 #define NERFACE_HIP_H
@@ -623,6 +624,17 @@ size_t nf_paper_mlp_fwd_live_scratch_floats(int max_workgroups);
 int nf_paper_mlp_fwd_live(const float* packed, const float* cond, const float* ro, const float* rd, const float* rd_view,
                           const float* z, int64_t n_rays, int n_samples, float* raw, float* scratch, size_t scratch_floats,
                           int max_workgroups, nf_stream_t stream);
+/* The kernel's waves take their work in units of 32 consecutive points from a counter in device memory that the library owns: the
+ * first launch on a device allocates the counters of that device (hipMalloc: make it outside a stream capture), no later one
+ * allocates.  Every launch zeroes its stream's counter on that stream in front of the kernel, so launches may follow each other on
+ * one stream without a synchronise and may be in flight together on several streams.
+ * nf_paper_mlp_fwd_live_stats: the same launch, same `raw`, through an instantiation of the kernel that records its schedule -- an
+ * instrument for tests and profiles, not a render path.  stats: int64 [stats_rows][4] on the device, 8-byte aligned, stats_rows >=
+ * 4 * (workgroups of the capped grid) = scratch floats / 4416; zeroed on the stream, then row (workgroup * 4 + wave) =
+ * (units of 32 points the wave took, colour runs with the final flush, rows of the final flush, wall_clock64() at exit).          */
+int nf_paper_mlp_fwd_live_stats(const float* packed, const float* cond, const float* ro, const float* rd, const float* rd_view,
+                                const float* z, int64_t n_rays, int n_samples, float* raw, float* scratch, size_t scratch_floats,
+                                int max_workgroups, int64_t* stats, size_t stats_rows, nf_stream_t stream);
 
 /* ---- isosurface of a dense grid (ABI 5 still: these only add) ------------------------------------------------------------------
  * grid: float32 [nz][ny][nx], x fastest; every axis n >= 2.  Marching tetrahedra on the Kuhn triangulation (DESIGN.md
