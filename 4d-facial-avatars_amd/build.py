@@ -23,7 +23,9 @@ SOURCES = ["nf_lib.hip", "nf_rays.hip", "nf_choice.hip", "nf_render.hip", "nf_re
            # the same kernel with a per-wave record of its schedule (an instrument: tests, profiles/live_dynamic.md)
            "nf_mlp_live_stats.hip",
            # marching tetrahedra on a dense grid
-           "nf_isosurface.hip"]
+           "nf_isosurface.hip",
+           # which points of a dense grid lie near the surface: evaluate those, +-inf elsewhere
+           "nf_sparse_grid.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-fvisibility=default",
          "-Wno-unused-result"]
 

@@ -22,7 +22,7 @@
 //                        k_iso_faces  inside bits -> triangles per cell -> scan -> face base; indices from vbase / mask of the owners
 // The order of every sum is fixed, so two calls give the same bits.  Memory-bound: 4 B per point read (the seven far corners come
 // from the cache), 2 + 4 B written, 1 + 1 B read again, plus the output.
-#include "nf_common.h"
+#include "nf_grid_dev.h"
 
 namespace nfi {
 constexpr int THREADS = 256;               // points per workgroup (4 waves), one block sum each (1024 was measured too: DESIGN.md)
@@ -164,29 +164,7 @@ extern "C" size_t nf_isosurface_workspace_bytes(int nx, int ny, int nz) {
     return nf_iso_plan(nx, ny, nz, &p) ? p.bytes : 0;
 }
 
-// ---- device helpers
-// inclusive sum over the workgroup's threads in thread order (wave64 shuffles, then the wave totals); *total = the workgroup's sum
-template <int WAVES>
-__device__ __forceinline__ uint32_t nf_iso_block_scan(uint32_t v, uint32_t* s_wave, uint32_t* total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t up = __shfl_up(v, o, 64);
-        if (lane >= o) v += up;
-    }
-    __syncthreads();                                            // s_wave may still be read from the previous call
-    if (lane == 63) s_wave[wave] = v;
-    __syncthreads();
-    uint32_t before = 0, all = 0;
-#pragma unroll
-    for (int w = 0; w < WAVES; ++w) {
-        const uint32_t t = s_wave[w];
-        before += w < wave ? t : 0u;
-        all += t;
-    }
-    *total = all;
-    return v + before;
-}
-
+// ---- device helpers (the workgroup scan nf_iso_block_scan and the index split nf_iso_point: nf_grid_dev.h)
 // triangles of a cell from the inside bits of its eight corners: per tetrahedron 1 for one or three corners inside, 2 for two (the
 // table's own counts, without a per-lane table read for every point of the grid)
 __device__ __forceinline__ uint32_t nf_iso_cell_tris(uint32_t inside) {
@@ -197,19 +175,6 @@ __device__ __forceinline__ uint32_t nf_iso_cell_tris(uint32_t inside) {
         n += in == 2u ? 2u : (in & 1u);
     }
     return n;
-}
-
-struct NfIsoPoint { int i, j, k; };
-
-// (i, j, k) of point p.  The plan keeps the number of points below 2^31, so the two divisions are 32-bit ones (a 64-bit division
-// is some hundred instructions, and every thread of k_iso_count takes two); everything that addresses memory stays 64-bit.
-__device__ __forceinline__ NfIsoPoint nf_iso_point(int64_t p, int nx, int ny) {
-    const uint32_t q = (uint32_t)p, row = q / (uint32_t)nx, k = row / (uint32_t)ny;
-    NfIsoPoint g;
-    g.i = (int)(q - row * (uint32_t)nx);
-    g.k = (int)k;
-    g.j = (int)(row - k * (uint32_t)ny);
-    return g;
 }
 
 __global__ void __launch_bounds__(nfi::THREADS) k_iso_count(const float* __restrict__ grid, int nx, int ny, int nz, float level, int64_t n_points,

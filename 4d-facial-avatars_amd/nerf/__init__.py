@@ -23,5 +23,6 @@ from .ops import training_loss  # MI355X extension: the trainer's loss (TR:355-3
 from .ops import get_mlp_precision, set_mlp_precision  # MI355X extension: "f32" (exact, default) | "f16x3" | "bf16x3" | "f16x2" (inference only)
 from .ops import image_metrics, quantize_image  # MI355X extension: L1 / PSNR / SSIM of uint8 frames on the device (nerf/metrics.py: two_folders)
 from .models import density  # MI355X extension: raw sigma of a fused model at arbitrary points, from the density-only kernels
+from .mesh import density_grid_sparse  # MI355X extension: that grid evaluated only in the bricks near one level's surface (ops.sparse_grid)
 from .mesh import Mesh, density_grid, extract_mesh, write_mesh  # MI355X extension: a model's density on a grid and the triangle mesh of one level (ops.isosurface)
 from .train_graph import GraphedTrainer  # MI355X extension: the training iteration captured once in a HIP graph and replayed (single rank)

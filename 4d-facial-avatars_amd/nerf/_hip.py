@@ -200,6 +200,13 @@ _PROTOTYPES["nf_isosurface_workspace_bytes"] = (_Z, [_I, _I, _I])
 _PROTOTYPES["nf_isosurface_count"] = (C.c_int, [_P, _I, _I, _I, _F, _P, _Z, _P, _P])
 _PROTOTYPES["nf_isosurface_emit"] = (C.c_int, [_P, _I, _I, _I, _F, _P, _P, _P, _Z, _P, _L, _P, _L, _P, _P])
 _PROTOTYPES["nf_isosurface_table"] = (C.c_int, [_P])
+# sparse evaluation of a dense grid: lattice, classify, mark (the counts on the device), emit, scatter (lo / hi are host float[3])
+_PROTOTYPES["nf_sparse_grid_workspace_bytes"] = (_Z, [_I, _I, _I, _I])
+_PROTOTYPES["nf_sparse_grid_lattice"] = (C.c_int, [_I, _I, _I, _I, _P, _P, _P, _P, _L, _P])
+_PROTOTYPES["nf_sparse_grid_classify"] = (C.c_int, [_P, _I, _I, _I, _I, _F, _F, _I, _P, _Z, _P])
+_PROTOTYPES["nf_sparse_grid_mark"] = (C.c_int, [_I, _I, _I, _I, _P, _Z, _P, _P])
+_PROTOTYPES["nf_sparse_grid_emit"] = (C.c_int, [_P, _I, _I, _I, _I, _P, _P, _P, _Z, _P, _P, _L, _P])
+_PROTOTYPES["nf_sparse_grid_scatter"] = (C.c_int, [_P, _P, _L, _P, _I, _I, _I, _P])
 for _prefix in ("nf_lcode", "nf_bshape", "nf_cbshape"):          # measurement hook (tools/time_blendshape.py)
     _PROTOTYPES[f"{_prefix}_mlp_bwd_stage_ms"] = (C.c_int, [_P, _P, _I, _P, _P, _P, _L, _I, _P, _Z, _P, _P, _P])
 # entry points that later ABI revisions add; absent symbols only fail when called

@@ -1,10 +1,12 @@
 """Geometry of a fused model: its raw density on a dense grid, the triangle mesh of one density level, and mesh files.
 
     density_grid(model, expr, latent_code, lo=, hi=, resolution=)          -> (nz, ny, nx) raw density on the device
+    density_grid_sparse(..., lo=, hi=, resolution=, level=, brick=)        -> the same grid evaluated near the surface only, and its stats
     extract_mesh(model, expr, latent_code, lo=, hi=, resolution=, level=)  -> Mesh(vertices, faces, normals), device tensors
     write_mesh(path, mesh)                                                 -> .off / .obj / .ply (binary little-endian), host code
 
-The density comes from the density-only kernels (nerf.density), the surface from ops.isosurface (csrc/nf_isosurface.hip).
+The density comes from the density-only kernels (nerf.density), the surface from ops.isosurface (csrc/nf_isosurface.hip), the choice
+of the points near the surface from ops.sparse_grid (csrc/nf_sparse_grid.hip).
 """
 from __future__ import annotations
 
@@ -24,13 +26,7 @@ class Mesh(NamedTuple):
     normals: Optional[torch.Tensor]              # (V, 3) float32 unit vectors towards lower density, or None
 
 
-def _resolution(resolution):
-    r = [int(resolution)] * 3 if np.isscalar(resolution) else [int(x) for x in resolution]
-    if len(r) == 1:
-        r = r * 3
-    if len(r) != 3 or min(r) < 2:
-        raise ValueError(f"resolution: one number or (nx, ny, nz), at least 2 points per axis, got {resolution}")
-    return r
+_resolution = ops._resolution
 
 
 def grid_axes(lo, hi, resolution):
@@ -61,11 +57,37 @@ def density_grid(model, expr, latent_code=None, *, lo, hi, resolution, chunk_poi
     return out
 
 
-def extract_mesh(model, expr, latent_code=None, *, lo, hi, resolution, level, normals: bool = True, chunk_points: int = 1 << 22) -> Mesh:
+def density_grid_sparse(model, expr, latent_code=None, *, lo, hi, resolution, level, brick: int = 8, margin: float = 0.0, dilate: int = 1,
+                        chunk_points: int = 1 << 22):
+    """density_grid evaluated only near the surface raw density == level: ops.sparse_grid with nerf.density of the model as its
+    function, under torch.no_grad().  Returns (grid, SparseGridStats): on the coarse lattice (the corners of the bricks of `brick`
+    cells) and in the active bricks the grid equals density_grid bit for bit, every other point holds +inf or -inf, the side of its
+    bricks' corners.  A brick is evaluated when its 8 corners are not all above level + margin or all below level - margin, or when
+    it lies within `dilate` bricks of such a brick: a feature thinner than a brick that passes between the corners is missed unless
+    `margin` is raised (ops.sparse_grid has the guarantee and its limit)."""
+    if not (torch.is_tensor(expr) and expr.is_cuda):
+        raise RuntimeError("nerf (MI355X build): tensors must live on a ROCm device (`device='cuda'`); there is no CPU path in this package")
+    with torch.no_grad():
+        return ops.sparse_grid(lambda pts: density(model, pts, expr, latent_code), float(level), lo, hi, resolution, brick=brick, margin=margin,
+                               dilate=dilate, chunk_points=chunk_points, device=expr.device)
+
+
+def extract_mesh(model, expr, latent_code=None, *, lo, hi, resolution, level, normals: bool = True, chunk_points: int = 1 << 22, brick=None,
+                 margin: float = 0.0, dilate: int = 1) -> Mesh:
     """The surface raw density == level of a fused model inside the box [lo, hi] for one expression (and latent code): density_grid,
     then ops.isosurface.  `level` is in raw-density units (before the ReLU of the volume renderer) and has no default: what counts
-    as surface depends on the scene's scale and on how the model was trained."""
-    grid = density_grid(model, expr, latent_code, lo=lo, hi=hi, resolution=resolution, chunk_points=chunk_points)
+    as surface depends on the scene's scale and on how the model was trained.  With `brick` (cells per brick, e.g. 8) the grid is
+    density_grid_sparse's: the network runs only in the bricks near the surface, and the mesh is the dense one wherever no brick
+    hides a feature between its corners (`margin`, `dilate`: ops.sparse_grid).  The normals reach one point past a brick, so they
+    need dilate >= 1."""
+    if brick is None:
+        grid = density_grid(model, expr, latent_code, lo=lo, hi=hi, resolution=resolution, chunk_points=chunk_points)
+    else:
+        brick, margin, dilate = ops.check_sparse_grid_args(brick, margin, dilate, "extract_mesh")
+        if normals and dilate == 0:
+            raise ValueError("extract_mesh: normals=True needs dilate >= 1 (the central differences reach into the neighbouring brick)")
+        grid, _ = density_grid_sparse(model, expr, latent_code, lo=lo, hi=hi, resolution=resolution, level=level, brick=brick, margin=margin,
+                                      dilate=dilate, chunk_points=chunk_points)
     return Mesh(*ops.isosurface(grid, float(level), lo, hi, normals=normals))
 
 

@@ -1168,3 +1168,99 @@ def isosurface(grid: torch.Tensor, level: float, lo, hi, normals: bool = False):
             H.check(lib.nf_isosurface_emit(H.ptr(grid), nx, ny, nz, float(level), C.addressof(c_lo), C.addressof(c_hi), H.ptr(ws), ws_bytes,
                                            H.ptr(verts), n_verts, H.ptr(faces), n_faces, H.ptr(norm), H.stream_ptr(dev)), "nf_isosurface_emit")
     return verts, faces, norm
+
+
+# ---------------------------------------------------------------------------------------- sparse evaluation of a dense grid
+class SparseGridStats(NamedTuple):
+    bricks: int                                  # bricks of the grid
+    seed_bricks: int                             # bricks whose 8 corners are not all on one side of the level (by more than the margin)
+    active_bricks: int                           # bricks within `dilate` bricks of a seed
+    points: int                                  # points of the grid
+    evaluated_points: int                        # points fn was asked for: the coarse lattice and the points of the active bricks
+
+
+def _resolution(resolution):
+    r = [int(resolution)] * 3 if np.isscalar(resolution) else [int(x) for x in resolution]
+    if len(r) == 1:
+        r = r * 3
+    if len(r) != 3 or min(r) < 2:
+        raise ValueError(f"resolution: one number or (nx, ny, nz), at least 2 points per axis, got {resolution}")
+    return r
+
+
+def check_sparse_grid_args(brick, margin, dilate, what: str = "sparse_grid"):
+    """(brick, margin, dilate) as int, float, int; ValueError for brick < 2, margin < 0 (or NaN) and dilate < 0."""
+    if int(brick) != brick or int(brick) < 2:
+        raise ValueError(f"{what}: brick is a whole number of cells, at least 2, got {brick}")
+    if not float(margin) >= 0.0:
+        raise ValueError(f"{what}: margin must be >= 0, got {margin}")
+    if int(dilate) != dilate or int(dilate) < 0:
+        raise ValueError(f"{what}: dilate is a whole number of bricks, at least 0, got {dilate}")
+    return int(brick), float(margin), int(dilate)
+
+
+def sparse_grid(fn, level: float, lo, hi, resolution, *, brick: int = 8, margin: float = 0.0, dilate: int = 1, chunk_points: int = 1 << 22,
+                device=None):
+    """The grid (nz, ny, nx) of fn on the `resolution` points spanning the box [lo, hi] (the points of nerf.mesh.grid_axes), with fn
+    evaluated only near the surface fn == level (DESIGN.md "Sparse density grid"; csrc/nf_sparse_grid.hip).  The grid is cut into
+    bricks of `brick` cells.  fn is first asked for the brick corners (the coarse lattice); a brick is a seed unless all 8 corners
+    are > level + margin or all are < level - margin; bricks within `dilate` bricks of a seed are active, and fn is asked for every
+    point of the active bricks.  Every other point holds +inf (its bricks' corners are inside, fn > level) or -inf (outside), which
+    ops.isosurface takes as any other value.
+
+    Provided every brick that is no seed really lies on one side of the level, and dilate >= 1, ops.isosurface gives on this grid
+    the vertices, faces and normals it gives on the dense grid, bit for bit (dilate = 0 keeps vertices and faces).  A feature thinner
+    than a brick that passes between the lattice points is missed: `margin` makes bricks whose corners come near the level seeds too.
+
+    fn maps an (n, 3) float32 device tensor to (n,) float32; it is called with at most `chunk_points` points per call, first for the
+    lattice and then for the other points, each in ascending linear index, and never twice for one point.  One host read: the three
+    counts.  Returns (grid, SparseGridStats); `device` defaults to the current ROCm device."""
+    nx, ny, nz = _resolution(resolution)
+    brick, margin, dilate = check_sparse_grid_args(brick, margin, dilate)
+    chunk = int(chunk_points)
+    if chunk < 1:
+        raise ValueError(f"sparse_grid: chunk_points must be at least 1, got {chunk_points}")
+    lo32, hi32 = _box(lo, hi, "sparse_grid")
+    lib = H.lib()
+    b = min(brick, 0x7fffffff)
+    ws_bytes = int(lib.nf_sparse_grid_workspace_bytes(nx, ny, nz, b))
+    if ws_bytes == 0:
+        raise ValueError(f"sparse_grid: a grid of {nx} x {ny} x {nz} points is past the plan of csrc/nf_isosurface.hip (7 * points and "
+                         "12 * cells stay below 2^31: vertex and face ids are int32)")
+    if not torch.cuda.is_available():
+        raise RuntimeError("nerf (MI355X build): sparse_grid runs on a ROCm device; there is no CPU path in this package")
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    bricks_per_axis = [-(-(n - 1) // brick) for n in (nx, ny, nz)]
+    n_bricks = int(np.prod(bricks_per_axis))
+    n_lattice = int(np.prod([m + 1 for m in bricks_per_axis]))
+    c_lo, c_hi = (C.c_float * 3)(*lo32.tolist()), (C.c_float * 3)(*hi32.tolist())
+    grid = torch.empty((nz, ny, nx), dtype=torch.float32, device=dev)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    counts = torch.empty(3, dtype=torch.int64, device=dev)
+
+    def evaluate(coords, index):
+        for c0 in range(0, coords.shape[0], chunk):
+            pts, idx = coords[c0:c0 + chunk], index[c0:c0 + chunk]
+            val = fn(pts)
+            if not torch.is_tensor(val) or val.shape != (pts.shape[0],) or val.device != grid.device:
+                raise ValueError(f"sparse_grid: fn must map ({pts.shape[0]}, 3) points to ({pts.shape[0]},) values on {grid.device}")
+            val = val.detach().to(torch.float32).contiguous()
+            H.check(lib.nf_sparse_grid_scatter(H.ptr(val), H.ptr(idx), idx.shape[0], H.ptr(grid), nx, ny, nz, H.stream_ptr(dev)),
+                    "nf_sparse_grid_scatter")
+
+    with torch.cuda.device(dev):
+        index = torch.empty(n_lattice, dtype=torch.int32, device=dev)
+        coords = torch.empty((n_lattice, 3), dtype=torch.float32, device=dev)
+        H.check(lib.nf_sparse_grid_lattice(nx, ny, nz, b, C.addressof(c_lo), C.addressof(c_hi), H.ptr(index), H.ptr(coords), n_lattice,
+                                           H.stream_ptr(dev)), "nf_sparse_grid_lattice")
+        evaluate(coords, index)
+        H.check(lib.nf_sparse_grid_classify(H.ptr(grid), nx, ny, nz, b, float(level), margin, min(dilate, 0x7fffffff), H.ptr(ws), ws_bytes,
+                                            H.stream_ptr(dev)), "nf_sparse_grid_classify")
+        H.check(lib.nf_sparse_grid_mark(nx, ny, nz, b, H.ptr(ws), ws_bytes, H.ptr(counts), H.stream_ptr(dev)), "nf_sparse_grid_mark")
+        n_seed, n_active, n_more = counts.tolist()                       # the one host read
+        index = torch.empty(n_more, dtype=torch.int32, device=dev)
+        coords = torch.empty((n_more, 3), dtype=torch.float32, device=dev)
+        H.check(lib.nf_sparse_grid_emit(H.ptr(grid), nx, ny, nz, b, C.addressof(c_lo), C.addressof(c_hi), H.ptr(ws), ws_bytes, H.ptr(index),
+                                        H.ptr(coords), n_more, H.stream_ptr(dev)), "nf_sparse_grid_emit")
+        evaluate(coords, index)
+    return grid, SparseGridStats(n_bricks, n_seed, n_active, nx * ny * nz, n_lattice + n_more)

@@ -658,6 +658,35 @@ int nf_isosurface_emit(const float* grid, int nx, int ny, int nz, float level, c
                        nf_stream_t stream);
 int nf_isosurface_table(uint32_t* out);
 
+/* ---- sparse evaluation of a dense grid around one level (ABI 5 still: these only add) -------------------------------------------
+ * The grid of the isosurface entry points, cut into bricks of `brick` >= 2 cells (DESIGN.md "Sparse density grid" is the
+ * specification): axis a has m = ceil((n - 1) / brick) bricks, the coarse lattice is the (mx + 1)(my + 1)(mz + 1) brick corners.
+ * The caller evaluates its function on the lattice, scatters the values into the grid, and then
+ *   nf_sparse_grid_classify  reads the 8 corners of every brick from `grid`: a brick is a seed unless all are > level + margin or
+ *                            all are < level - margin (float32 sums; NaN makes a seed), active within `dilate` bricks of a seed;
+ *   nf_sparse_grid_mark      counts the points of active bricks that are no lattice points; counts_dev[0..2] = seed bricks, active
+ *                            bricks, points to evaluate (int64, on the device);
+ *   nf_sparse_grid_emit      writes their linear indices (ascending) and coordinates lo + i * h (multiply, then add; h = (hi - lo) /
+ *                            (n - 1) in float32) to index / coords, and +inf / -inf into every grid point that is neither listed nor
+ *                            on the lattice: the side (v > level or not) of the corners of the bricks it lies in.
+ * `capacity` is the size of index / coords in rows: nf_sparse_grid_lattice needs at least the lattice's size; nf_sparse_grid_emit
+ * writes no row at or past it.  nf_sparse_grid_scatter: grid[index[t]] = values[t] for t < count; an index outside the grid
+ * writes nothing.  workspace: nf_sparse_grid_workspace_bytes(nx, ny, nz, brick) bytes, 8-byte aligned, the same buffer through
+ * classify, mark and emit; 0 = a size that is not served (an axis below 2, brick below 2, or a grid past nf_isosurface's plan).
+ * lo, hi: HOST float[3].  NF_EINVAL before any device call: NULL pointers, an unserved size, workspace_bytes or capacity too small,
+ * !(lo < hi) on an axis, margin < 0 or NaN, dilate < 0, count < 0 or above the grid's points.  Two calls give the same bits.    */
+size_t nf_sparse_grid_workspace_bytes(int nx, int ny, int nz, int brick);
+int nf_sparse_grid_lattice(int nx, int ny, int nz, int brick, const float* lo, const float* hi, int* index, float* coords,
+                           int64_t capacity, nf_stream_t stream);
+int nf_sparse_grid_classify(const float* grid, int nx, int ny, int nz, int brick, float level, float margin, int dilate,
+                            void* workspace, size_t workspace_bytes, nf_stream_t stream);
+int nf_sparse_grid_mark(int nx, int ny, int nz, int brick, void* workspace, size_t workspace_bytes, int64_t* counts_dev,
+                        nf_stream_t stream);
+int nf_sparse_grid_emit(float* grid, int nx, int ny, int nz, int brick, const float* lo, const float* hi, void* workspace,
+                        size_t workspace_bytes, int* index, float* coords, int64_t capacity, nf_stream_t stream);
+int nf_sparse_grid_scatter(const float* values, const int* index, int64_t count, float* grid, int nx, int ny, int nz,
+                           nf_stream_t stream);
+
 /* ---- host-only self-tests (no device needed): consistency of the weight-gradient job tables -- every slab entry written
  * exactly once per slice, tile ids inside their bundle.  0 = consistent, negative = which check failed.                 */
 int nf_selftest_dw_tables_f32(void);
