@@ -22,6 +22,8 @@ SOURCES = ["nf_lib.hip", "nf_rays.hip", "nf_choice.hip", "nf_render.hip", "nf_re
            "nf_mlp_live.hip",
            # the same kernel with a per-wave record of its schedule (an instrument: tests, profiles/live_dynamic.md)
            "nf_mlp_live_stats.hip",
+           # the live-colour kernel with fc_feat, too, only where a bound on sigma cannot prove the sample dead; its statistics twin
+           "nf_mlp_gated.hip", "nf_mlp_gated_stats.hip",
            # marching tetrahedra on a dense grid
            "nf_isosurface.hip",
            # which points of a dense grid lie near the surface: evaluate those, +-inf elsewhere
@@ -39,7 +41,8 @@ UNIT_FLAGS = {u: ["-fno-slp-vectorize"] for u in ("nf_mlp_f16.hip", "nf_mlp_f16x
 # The live-colour kernel takes its next unit of work with a one-lane atomicAdd whose result it reads a whole pass later.  The atomic
 # optimiser would rewrite that add for "any number of active lanes" and read the result back with v_readfirstlane on the spot: a wait
 # for the counter's round trip at the top of every pass.
-UNIT_FLAGS.update({u: ["-mllvm", "-amdgpu-atomic-optimizer-strategy=None"] for u in ("nf_mlp_live.hip", "nf_mlp_live_stats.hip")})
+UNIT_FLAGS.update({u: ["-mllvm", "-amdgpu-atomic-optimizer-strategy=None"] for u in ("nf_mlp_live.hip", "nf_mlp_live_stats.hip",
+                                                                                            "nf_mlp_gated.hip", "nf_mlp_gated_stats.hip")})
 
 
 def _hipcc() -> str:

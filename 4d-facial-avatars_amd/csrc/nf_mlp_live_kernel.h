@@ -1,5 +1,7 @@
 // k_paper_mlp_fwd_live and what launches it: the kernel of nf_mlp_live.hip (the description stands there), written once for its two
-// instantiations -- the production kernel (nf_mlp_live.hip) and the one that also counts what each wave did (nf_mlp_live_stats.hip).
+// instantiations -- the production kernel (nf_mlp_live.hip) and the one that also counts what each wave did (nf_mlp_live_stats.hip) --
+// and for k_paper_mlp_fwd_live<., ., GATE> (GATE; nf_mlp_gated.hip, nf_mlp_gated_stats.hip: the description stands there), the same schedule
+// with "not proven dead" in place of "live" and fc_feat moved into the gathered run.
 #pragma once
 #include <mutex>
 #include "nf_mlp_paper_net.h"
@@ -69,31 +71,67 @@ struct NfLivePre {
     }
 };
 
+// GATE: what a pass requests while the bound tile runs alone -- fc_feat's bias and first weight chunk as the gathered run finds them,
+// and the oldest ring rows.  The bound image's descriptor is made where it is used, from the pointer's VGPR home.
+struct NfGatePre {
+    NfStream<NF_MLP_NT>& st;
+    f32x4 (&pf)[NF_LIVE_PF > 0 ? NF_LIVE_PF : 1];
+    char* ring_v;
+    int head_v, tail_v;
+    const float* bound_v;
+    __device__ __forceinline__ NfW image() const {
+        const uint64_t a = (uint64_t)bound_v;
+        const uint64_t s = (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)a) |
+                           ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(a >> 32)) << 32);
+        return nf_w_image(reinterpret_cast<const float*>(s), NF_BOUND_FLOATS);
+    }
+    __device__ __forceinline__ void wait() const {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        __builtin_amdgcn_s_waitcnt(0x0F70);               // vmcnt(0)
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    }
+    __device__ __forceinline__ void loads(const NfW& Wi, const NfW& Ci, int lane) {
+        using Net = NfPaperNet;
+        const __amdgpu_buffer_rsrc_t ring = nf_live_ring(ring_v);
+        const int tail = __builtin_amdgcn_readfirstlane(tail_v), cnt = __builtin_amdgcn_readfirstlane(head_v) - tail;
+#pragma unroll
+        for (int i = 0; i < NF_LIVE_PF; ++i)
+            pf[i] = nf_live_load(ring, i < cnt ? ((tail + i) & (NF_LIVE_ROWS - 1)) * 1024 + lane * 16 : NF_LIVE_OOB);
+        nf_load_bias<16>(st.bias, Ci, Net::B_FEAT, lane);
+        nf_load_w16<16>(st.wa, Wi, Net::OFF_FEAT / 4, lane);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+};
+
 // What the STATS instantiation writes per wave, row (blockIdx.x * NF_MLP_WAVES + wave) of `stats` (zero when the launch starts):
 #define NF_LIVE_STAT_UNITS 0                              // units taken (the one past the end that ends the wave is not counted)
 #define NF_LIVE_STAT_RUNS 1                               // colour runs, the final flush included
 #define NF_LIVE_STAT_FLUSH 2                              // rows of the final flush
 #define NF_LIVE_STAT_CLOCK 3                              // wall_clock64() at exit
 #define NF_LIVE_STAT_COLS 4
+#define NF_GATE_STAT_PROVEN 4                             // GATE: rows proven dead (a fifth column; the first four as above, "colour run" =
+#define NF_GATE_STAT_COLS 5                               // gathered run)
 
 // one lane of the wave adds to its row; the row belongs to the wave, and nothing is held in a register across the trunk
-template <bool STATS>
+template <bool STATS, int COLS = NF_LIVE_STAT_COLS>
 __device__ __forceinline__ void nf_live_stat(long long* stats, int col, long long add, bool set = false) {
     if constexpr (STATS) {
         if ((threadIdx.x & 63) == 0) {
-            long long* at = stats + ((size_t)blockIdx.x * NF_MLP_WAVES + (threadIdx.x >> 6)) * NF_LIVE_STAT_COLS + col;
+            long long* at = stats + ((size_t)blockIdx.x * NF_MLP_WAVES + (threadIdx.x >> 6)) * COLS + col;
             *at = set ? add : *at + add;
         }
     }
 }
 
-template <int NT, bool STATS>
+// GATE: the kernel of nf_mlp_gated.hip; `bound` is the sigma-bound image of `packed` (not read otherwise).
+template <int NT, bool STATS, bool GATE = false>
 __global__ void __launch_bounds__(64 * NF_MLP_WAVES, 1)
 k_paper_mlp_fwd_live(const float* __restrict__ packed, const float* __restrict__ cond_, const float* __restrict__ ro,
                      const float* __restrict__ rd, const float* __restrict__ rd_view, const float* __restrict__ z,
                      int64_t n_points, int S, float* __restrict__ raw, float* __restrict__ scratch, unsigned* __restrict__ counter,
-                     long long* __restrict__ stats) {
+                     long long* __restrict__ stats, const float* __restrict__ bound) {
     using Net = NfPaperNet;
+    constexpr int COLS = GATE ? NF_GATE_STAT_COLS : NF_LIVE_STAT_COLS;
     __shared__ __attribute__((aligned(16))) f32x4 lds[NF_MLP_WAVES * 16 * NT * 64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     f32x4* act4 = lds + wave * (16 * NT * 64);
@@ -106,6 +144,8 @@ k_paper_mlp_fwd_live(const float* __restrict__ packed, const float* __restrict__
     const float* z_v = z;
     const float* rdv_v = rd_view;
     asm volatile("" : "+v"(z_v), "+v"(rdv_v));
+    const float* bound_v = bound;
+    if constexpr (GATE) asm volatile("" : "+v"(bound_v));
     int head_v = 0, tail_v = 0;                           // rows appended / consumed so far (row = count & 63); head - tail <= 31
     asm volatile("" : "+v"(head_v), "+v"(tail_v));
     // Unit u is points 32 u .. 32 u + 31, and a wave takes its units from the launch's counter (zero when the launch starts), one at
@@ -131,7 +171,7 @@ k_paper_mlp_fwd_live(const float* __restrict__ packed, const float* __restrict__
         // units + waves to the counter.)
         unsigned next_v = 0;
         if (more && lane == 0) next_v = __hip_atomic_fetch_add(ctr_v, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (more) nf_live_stat<STATS>(stats, NF_LIVE_STAT_UNITS, 1);
+        if (more) nf_live_stat<STATS, COLS>(stats, NF_LIVE_STAT_UNITS, 1);
         int opaque0 = 0;                                  // per-block opaque zero: the weight / bias loads must stay where the layers issue them
         asm volatile("" : "+s"(opaque0));
         const NfW Wi = nf_w_image(packed + opaque0, Net::PACKED), Ci = nf_w_image(cond_ + opaque0, Net::COND_FLOATS);
@@ -139,12 +179,28 @@ k_paper_mlp_fwd_live(const float* __restrict__ packed, const float* __restrict__
         f32x4 wd[16], pf[NF_LIVE_PF > 0 ? NF_LIVE_PF : 1];
         f32x4 dirf[NT][1];
         float sigma_own[NT];
+        // GATE: sigma_own is the bound s + 2^-13 u of the pass's own rows -- what a proven row gets for its density -- and "live" reads
+        // "not proven dead"; tag_own is nonzero bits on a ray's last sample (the third word of a meta row, in sigma_raw's place: the
+        // gathered run computes the density itself and needs to know whether a row that turns out dead keeps its colour)
+        float tag_own[NT] = {};
+        bool proven[NT] = {};
         int live_v = 0, run_v = 0;                        // the pass's 32-bit liveness mask; nonzero: the colour layers run
         if (more) {
             f32x4 pe[NT][4];
             nf_net_inputs<NT>(pe, dirf, p0, n_points, S, lane, ro, rd, rdv_v, z_v);
             f32x4 acc[NT][16];
-            nf_paper_net_body<Net, NT, 1, true>(acc, sigma_own, pe, dirf, Wi, Ci, act4, lane, NfLivePre{st, wd, pf, ring_v, head_v, tail_v});
+            if constexpr (GATE) {
+                nf_paper_net_body<Net, NT, 1, true, NfGatePre, true>(acc, sigma_own, pe, dirf, Wi, Ci, act4, lane,
+                                                                     NfGatePre{st, pf, ring_v, head_v, tail_v, bound_v});
+#pragma unroll
+                for (int t = 0; t < NT; ++t) {             // proven dead iff s + 2^-13 u < -2^-100, false for NaN or infinite operands
+                    const float s = acc[t][8].x, u = acc[t][8].y;
+                    sigma_own[t] = nf_add(s, nf_mul(u, 0x1p-13f));
+                    proven[t] = sigma_own[t] < -0x1p-100f && s > -INFINITY && u < INFINITY;
+                }
+            } else {
+                nf_paper_net_body<Net, NT, 1, true>(acc, sigma_own, pe, dirf, Wi, Ci, act4, lane, NfLivePre{st, wd, pf, ring_v, head_v, tail_v});
+            }
             int lane_o = lane;
             asm volatile("" : "+v"(lane_o));
             const int g = lane_o >> 4, c = lane_o & 15;
@@ -157,12 +213,17 @@ k_paper_mlp_fwd_live(const float* __restrict__ packed, const float* __restrict__
 #pragma unroll
             for (int t = 0; t < NT; ++t) {
                 const int64_t p = p0_o + 16 * t + c;
-                const bool is_live = g == 0 && p < n_points && (!(sigma_own[t] <= 0.0f) || (p + 1) % S_o == 0);
+                const bool is_live = g == 0 && p < n_points && ((GATE ? !proven[t] : !(sigma_own[t] <= 0.0f)) || (p + 1) % S_o == 0);
+                if constexpr (GATE) tag_own[t] = __int_as_float((p + 1) % S_o == 0 ? 1 : 0);
                 live |= ((unsigned)__builtin_amdgcn_ballot_w64(is_live) & 0xffffu) << (16 * t);
             }
             const int head = __builtin_amdgcn_readfirstlane(head_v), cnt = head - __builtin_amdgcn_readfirstlane(tail_v);
             const int n_live = __builtin_popcount(live);
             live_v = (int)live;
+            if constexpr (GATE) {                         // (in-range rows that are not kept are the proven ones)
+                const int64_t left = n_points - p0_o;
+                nf_live_stat<STATS, COLS>(stats, NF_GATE_STAT_PROVEN, (left < 16 * NT ? (int)left : 16 * NT) - n_live);
+            }
             if (cnt + n_live >= 16 * NT) {                // the ring fills every hole
                 run_v = 1;
             } else {                                      // append the live rows; nothing runs
@@ -191,7 +252,7 @@ k_paper_mlp_fwd_live(const float* __restrict__ packed, const float* __restrict__
                         if (g == 0) {
                             const int64_t p = p0_o + bit;
                             nf_live_store(ring, NF_LIVE_META_B + row * 16,
-                                          (f32x4){__int_as_float((int)(uint32_t)p), __int_as_float((int)(p >> 32)), sigma_own[t], 0.0f});
+                                          (f32x4){__int_as_float((int)(uint32_t)p), __int_as_float((int)(p >> 32)), GATE ? tag_own[t] : sigma_own[t], 0.0f});
                         }
                     }
                 }
@@ -201,9 +262,15 @@ k_paper_mlp_fwd_live(const float* __restrict__ packed, const float* __restrict__
         } else {
             // behind the wave's last block: what the ring holds goes to rows 0 .. R - 1 of the slab.  (The requests are made with an
             // empty ring too, once per wave: every path into the colour run below defines what it reads.)
-            NfLivePre pre{st, wd, pf, ring_v, head_v, tail_v};
-            pre.wait();
-            pre.loads(Wi, Ci, lane);
+            if constexpr (GATE) {
+                NfGatePre pre{st, pf, ring_v, head_v, tail_v, bound_v};
+                pre.wait();
+                pre.loads(Wi, Ci, lane);
+            } else {
+                NfLivePre pre{st, wd, pf, ring_v, head_v, tail_v};
+                pre.wait();
+                pre.loads(Wi, Ci, lane);
+            }
 #pragma unroll
             for (int t = 0; t < NT; ++t) {
                 dirf[t][0] = (f32x4){0.0f, 0.0f, 0.0f, 0.0f};
@@ -214,8 +281,8 @@ k_paper_mlp_fwd_live(const float* __restrict__ packed, const float* __restrict__
         asm volatile("" : "+v"(live_v), "+v"(run_v));
         const int run = __builtin_amdgcn_readfirstlane(run_v);
         if (run != 0) {
-            nf_live_stat<STATS>(stats, NF_LIVE_STAT_RUNS, 1);
-            if (run == 2) nf_live_stat<STATS>(stats, NF_LIVE_STAT_FLUSH, __builtin_amdgcn_readfirstlane(head_v) - __builtin_amdgcn_readfirstlane(tail_v));
+            nf_live_stat<STATS, COLS>(stats, NF_LIVE_STAT_RUNS, 1);
+            if (run == 2) nf_live_stat<STATS, COLS>(stats, NF_LIVE_STAT_FLUSH, __builtin_amdgcn_readfirstlane(head_v) - __builtin_amdgcn_readfirstlane(tail_v));
             int lane_o = lane;
             asm volatile("" : "+v"(lane_o));
             const int g = lane_o >> 4, c = lane_o & 15;
@@ -236,7 +303,7 @@ k_paper_mlp_fwd_live(const float* __restrict__ packed, const float* __restrict__
                 const f32x4 fm = nf_live_load(ring, f ? NF_LIVE_META_B + row * 16 : NF_LIVE_OOB);
                 const int64_t p = (p0_v) + bit;
                 dirf[t][0] = f ? fd : dirf[t][0];
-                meta[t] = f ? fm : (f32x4){__int_as_float((int)(uint32_t)p), __int_as_float((int)(p >> 32)), sigma_own[t], 0.0f};
+                meta[t] = f ? fm : (f32x4){__int_as_float((int)(uint32_t)p), __int_as_float((int)(p >> 32)), GATE ? tag_own[t] : sigma_own[t], 0.0f};
                 valid[t] = f || ((own >> bit) & 1u);
             }
             // the rows themselves: the prefetched ones from their registers, the others loaded here
@@ -264,13 +331,22 @@ k_paper_mlp_fwd_live(const float* __restrict__ packed, const float* __restrict__
             }
             // layers_dir.0 starts as a layer's tail would leave it: bias and first weight chunk requested (NfLivePre), first B fragment
             // as stored.  Output tiles 0 .. 7 only; the weight image keeps its 9-tile chunk stride.
+            // GATE: the slab holds layers_xyz.5's accumulators, and fc_feat starts the same way (NfGatePre); behind it layers_dir.0 in its
+            // full nine-tile form, fc_alpha as tile 8: the MFMAs of k_paper_mlp_fwd from fc_feat on, in its order.
             constexpr int NDIR = 1;
             constexpr unsigned D0 = Net::OFF_D0 / 4;
             nf_read_b<NT>(st.b0, act4, lane, 0);
             f32x4 acc[NT][16], bj[NT];
             float sigma_raw[NT];
-            NF_NET_COLOUR_D0(8, 9, wd);
-            NF_NET_COLOUR_REST();
+            if constexpr (GATE) {
+                nf_seg_lds<NT, 16, true, true>(acc, st, Wi, Net::OFF_FEAT / 4, 16, act4, lane);
+                nf_pending_b<NT, true>(bj, st);
+                nf_tail<NT, 16, 16, 9, 1>(acc, st.wb, bj, st, Wi, D0, Ci, Net::B_D0, act4, lane);
+                NF_NET_COLOUR();
+            } else {
+                NF_NET_COLOUR_D0(8, 9, wd);
+                NF_NET_COLOUR_REST();
+            }
             int lane_s = lane;
             asm volatile("" : "+v"(lane_s));
             if ((lane_s >> 4) == 0) {
@@ -278,7 +354,13 @@ k_paper_mlp_fwd_live(const float* __restrict__ packed, const float* __restrict__
                 for (int t = 0; t < NT; ++t) {
                     if (valid[t]) {
                         const int64_t p = (int64_t)(uint32_t)__float_as_int(meta[t].x) | ((int64_t)__float_as_int(meta[t].y) << 32);
-                        if (p >= 0 && p < n_points) raw_v[p] = (f32x4){acc[t][0].x, acc[t][0].y, acc[t][0].z, meta[t].z};
+                        if constexpr (GATE) {             // a gathered row that turns out dead: rgb 0 and its exact density
+                            const bool keep = !(sigma_raw[t] <= 0.0f) || __float_as_int(meta[t].z) != 0;
+                            if (p >= 0 && p < n_points)
+                                raw_v[p] = (f32x4){keep ? acc[t][0].x : 0.0f, keep ? acc[t][0].y : 0.0f, keep ? acc[t][0].z : 0.0f, sigma_raw[t]};
+                        } else {
+                            if (p >= 0 && p < n_points) raw_v[p] = (f32x4){acc[t][0].x, acc[t][0].y, acc[t][0].z, meta[t].z};
+                        }
                     }
                 }
             }
@@ -301,9 +383,8 @@ k_paper_mlp_fwd_live(const float* __restrict__ packed, const float* __restrict__
         asm volatile("" : "+v"(next_v));
         unit_v = next_v;
     }
-    nf_live_stat<STATS>(stats, NF_LIVE_STAT_CLOCK, (long long)wall_clock64(), true);
+    nf_live_stat<STATS, COLS>(stats, NF_LIVE_STAT_CLOCK, (long long)wall_clock64(), true);
 }
-
 
 // a grid capped at max_workgroups (0: one workgroup per CU of the current device)
 static inline int64_t nf_live_grid_cap(int max_workgroups) {
@@ -359,13 +440,14 @@ inline unsigned* nf_live_counter(hipStream_t stream) {
 
 // Argument checks and launch of either instantiation (stats: null for the production kernel).  A unit number is 32 bits wide and the
 // counter ends at units + waves: more than 2^31 units (2^36 points) are refused.
-template <bool STATS>
+template <bool STATS, bool GATE = false>
 static inline int nf_live_launch(const float* packed, const float* cond, const float* ro, const float* rd, const float* rd_view, const float* z,
                                  int64_t n_rays, int n_samples, float* raw, float* scratch, size_t scratch_floats, int max_workgroups,
-                                 long long* stats, nf_stream_t stream) {
+                                 long long* stats, nf_stream_t stream, const float* bound = nullptr) {
     static_assert(NF_MLP_WAVES * 16 * NF_MLP_NT == 128, "nf_mlp_fwd_launch sizes the grid for 128 points per workgroup");
     if (max_workgroups < 0 || !scratch || ((uintptr_t)scratch & 15) ||
-        scratch_floats < (size_t)nf_live_grid_cap(max_workgroups) * NF_MLP_WAVES * (NF_LIVE_WAVE_B / 4))
+        scratch_floats < (size_t)nf_live_grid_cap(max_workgroups) * NF_MLP_WAVES * (NF_LIVE_WAVE_B / 4) ||
+        (GATE && (!bound || ((uintptr_t)bound & 15))))
         return NF_EINVAL;
     const float* rdv = rd_view ? rd_view : rd;
     int rc = 0;
@@ -385,8 +467,8 @@ static inline int nf_live_launch(const float* packed, const float* cond, const f
             return;
         }
         const int64_t cap = nf_live_grid_cap(max_workgroups);
-        hipLaunchKernelGGL((k_paper_mlp_fwd_live<NF_MLP_NT, STATS>), dim3((unsigned)(grid < cap ? grid : cap)), dim3(64 * NF_MLP_WAVES), 0,
-                           nf_s(stream), packed, cond, ro, rd, rdv, z, n_points, n_samples, raw, scratch, counter, stats);
+        hipLaunchKernelGGL((k_paper_mlp_fwd_live<NF_MLP_NT, STATS, GATE>), dim3((unsigned)(grid < cap ? grid : cap)), dim3(64 * NF_MLP_WAVES), 0,
+                           nf_s(stream), packed, cond, ro, rd, rdv, z, n_points, n_samples, raw, scratch, counter, stats, bound);
     });
     return rc ? rc : launched;
 }

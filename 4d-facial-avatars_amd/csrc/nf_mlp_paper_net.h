@@ -257,14 +257,52 @@ static inline dim3 nf_paper_net_condition_grid() { return dim3((Net::COND_FLOATS
 // behind the layer are neither fetched nor issued.  Leaves sigma_raw[t]; acc[t][0] is not a colour.  While that tile runs alone the
 // other accumulator tiles are dead: `pre` (SIGMA only) may request what the caller wants next -- pre.wait() stands in front of
 // fc_alpha's weight loads, pre.loads() behind them (k_paper_mlp_fwd_live, nf_mlp_live.hip; NfNoPre: nothing).
+// GATE (with SIGMA; a family with layers_xyz.5): the trunk ends one layer earlier.  Behind layers_xyz.5 one tile of 16 rows runs
+// alone over relu(layers_xyz.5) -- the sigma-bound tile of pre.image() (nf_mlp_gated.hip: rows 0 and 1 are the folded fc_alpha . fc_feat
+// and its absolute-value twin, its bias fragment follows its 16 chunks) -- where SIGMA runs fc_alpha's; fc_feat is not issued.  Leaves
+// the tile in acc[t][8] (lane group 0: .x = row 0, .y = row 1 of point 16 t + c) and layers_xyz.5's accumulators, as stored, in the slab.
 struct NfNoPre {
     __device__ __forceinline__ void wait() const {}
     __device__ __forceinline__ void loads(const NfW&, const NfW&, int) const {}
 };
-template <class Net, int NT, int NDIR, bool SIGMA = false, class Pre = NfNoPre>
+#define NF_BOUND_BIAS 4096                                    // float offset of the bound image's bias fragment (row r of the tile at + r)
+#define NF_BOUND_FLOATS (NF_BOUND_BIAS + 16)
+// One tile of 16 output rows alone over the slab's 16 chunks (weights: f32x4 index first4 + ch * stride4 of W, chunk 0 already in
+// st.wa[0], bias in st.bias[0], first B fragment in st.b0), into acc[t][8].  The other accumulator tiles are dead meanwhile: pre.wait()
+// stands in front of the tile's weight loads, pre.loads() behind them.
+template <int NT, bool RELU_IN, class Pre>
+__device__ __forceinline__ void nf_net_lone_tile(f32x4 (&acc)[NT][16], const NfStream<NT>& st, f32x4 (&bj)[NT], const NfW& W, unsigned first4,
+                                                 unsigned stride4, const NfW& Wi, const NfW& Ci, const f32x4* act4, int lane, Pre& pre) {
+    f32x4 w8[16];
+    w8[0] = st.wa[0];
+    pre.wait();
+#pragma unroll
+    for (int ch = 1; ch < 16; ++ch) w8[ch] = nf_load_w1(W, first4 + stride4 * ch, lane);
+    pre.loads(Wi, Ci, lane);
+#pragma unroll
+    for (int ch = 0; ch < 16; ++ch) {
+        if (ch == 0) {
+#pragma unroll
+            for (int t = 0; t < NT; ++t) bj[t] = RELU_IN ? nf_relu_i(st.b0[t]) : st.b0[t];
+        } else {
+            nf_read_b<NT>(bj, act4, lane, ch);
+            if (RELU_IN) {
+#pragma unroll
+                for (int t = 0; t < NT; ++t) bj[t] = nf_relu_i(bj[t]);
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+#pragma unroll
+            for (int t = 0; t < NT; ++t)
+                acc[t][8] = __builtin_amdgcn_mfma_f32_16x16x4f32(w8[ch][r], bj[t][r], (ch == 0 && r == 0) ? st.bias[0] : acc[t][8], 0, 0, 0);
+    }
+}
+template <class Net, int NT, int NDIR, bool SIGMA = false, class Pre = NfNoPre, bool GATE = false>
 __device__ __forceinline__ void nf_paper_net_body(f32x4 (&acc)[NT][16], float (&sigma_raw)[NT], const f32x4 (&pe)[NT][4],
                                                   const f32x4 (&dirf)[NT][NDIR], const NfW& Wi, const NfW& Ci, f32x4* act4, int lane,
                                                   Pre pre = Pre()) {
+    static_assert(!GATE || (SIGMA && Net::HAS_L5), "the bound tile stands in for fc_alpha's lone tile, behind layers_xyz.5");
     constexpr unsigned D0 = (NDIR == 1 ? Net::OFF_D0 : Net::OFF_D0E) / 4;
     NfStream<NT> st;
     f32x4 bj[NT];
@@ -278,7 +316,15 @@ __device__ __forceinline__ void nf_paper_net_body(f32x4 (&acc)[NT][16], float (&
     NF_NET_LAYER256(Net::OFF_L2 / 4, true, Net::OFF_L3 / 4, Net::B_L3, 16, 0);
     NF_NET_L3_PE();
     NF_NET_LAYER256(Net::OFF_L3 / 4 + 4 * 16 * 64, false, Net::OFF_L4 / 4, Net::B_L4, 16, 1);
-    if constexpr (Net::HAS_L5) {
+    if constexpr (GATE) {
+        NF_NET_LAYER256(Net::OFF_L4 / 4, true, Net::OFF_L5 / 4, Net::B_L5, 16, 1);
+        const NfW Bi = pre.image();
+        nf_seg_lds<NT, 16, true, true>(acc, st, Wi, Net::OFF_L5 / 4, 16, act4, lane);
+        nf_pending_b<NT, true>(bj, st);
+        nf_tail<NT, 16, 16, 1, 1>(acc, st.wb, bj, st, Bi, 0, Bi, NF_BOUND_BIAS, act4, lane);
+        nf_net_lone_tile<NT, true>(acc, st, bj, Bi, 0, 64, Wi, Ci, act4, lane, pre);
+        return;
+    } else if constexpr (Net::HAS_L5) {
         NF_NET_LAYER256(Net::OFF_L4 / 4, true, Net::OFF_L5 / 4, Net::B_L5, 16, 1);
         NF_NET_LAYER256(Net::OFF_L5 / 4, true, Net::OFF_FEAT / 4, Net::B_FEAT, 16, 1);
     } else {
@@ -287,26 +333,7 @@ __device__ __forceinline__ void nf_paper_net_body(f32x4 (&acc)[NT][16], float (&
     // fc_feat (no activation: layers_dir.0 reads it as stored)
     if constexpr (SIGMA) {
         NF_NET_LAYER256(Net::OFF_FEAT / 4, true, D0 + 8 * 64, Net::B_D0 + 128, 1, 1);      // next: tile 8 alone, its bias fragment
-        f32x4 w8[16];
-        w8[0] = st.wa[0];
-        pre.wait();
-#pragma unroll
-        for (int ch = 1; ch < 16; ++ch) w8[ch] = nf_load_w1(Wi, D0 + (9 * ch + 8) * 64, lane);
-        pre.loads(Wi, Ci, lane);
-#pragma unroll
-        for (int ch = 0; ch < 16; ++ch) {
-            if (ch == 0) {
-#pragma unroll
-                for (int t = 0; t < NT; ++t) bj[t] = st.b0[t];
-            } else {
-                nf_read_b<NT>(bj, act4, lane, ch);
-            }
-#pragma unroll
-            for (int r = 0; r < 4; ++r)
-#pragma unroll
-                for (int t = 0; t < NT; ++t)
-                    acc[t][8] = __builtin_amdgcn_mfma_f32_16x16x4f32(w8[ch][r], bj[t][r], (ch == 0 && r == 0) ? st.bias[0] : acc[t][8], 0, 0, 0);
-        }
+        nf_net_lone_tile<NT, false>(acc, st, bj, Wi, D0 + 8 * 64, 9 * 64, Wi, Ci, act4, lane, pre);
 #pragma unroll
         for (int t = 0; t < NT; ++t) sigma_raw[t] = acc[t][8].x;
         return;

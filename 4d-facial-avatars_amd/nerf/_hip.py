@@ -195,6 +195,11 @@ _PROTOTYPES["nf_paper_mlp_fwd_live_scratch_floats"] = (_Z, [_I])
 _PROTOTYPES["nf_paper_mlp_fwd_live"] = (C.c_int, [_P, _P, _P, _P, _P, _P, _L, _I, _P, _P, _Z, _I, _P])
 # the same launch through the instantiation that records its schedule: + (stats, stats_rows) in front of the stream
 _PROTOTYPES["nf_paper_mlp_fwd_live_stats"] = (C.c_int, [_P, _P, _P, _P, _P, _P, _L, _I, _P, _P, _Z, _I, _P, _Z, _P])
+# fc_feat only where the sigma bound cannot prove a sample dead: the bound image of a packed image, then mlp_fwd_live + (bound)
+_PROTOTYPES["nf_paper_sigma_bound_floats"] = (_Z, [])
+_PROTOTYPES["nf_paper_sigma_bound"] = (C.c_int, [_P, _P, _P])
+_PROTOTYPES["nf_paper_mlp_fwd_gated"] = (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _L, _I, _P, _P, _Z, _I, _P])
+_PROTOTYPES["nf_paper_mlp_fwd_gated_stats"] = (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _L, _I, _P, _P, _Z, _I, _P, _Z, _P])
 # isosurface of a dense grid: count (workspace, V and F on the device), then emit (lo / hi are host float[3])
 _PROTOTYPES["nf_isosurface_workspace_bytes"] = (_Z, [_I, _I, _I])
 _PROTOTYPES["nf_isosurface_count"] = (C.c_int, [_P, _I, _I, _I, _F, _P, _Z, _P, _P])

@@ -35,7 +35,9 @@ class _FusedNeRFModel(torch.nn.Module):
     def hip_forward(self, ro, rd, z, rd_view, expr, latent, near, far, need_grad, live_only=False):
         """raw (R, S, 4) for the points ro + rd*z in the arithmetic of nerf.set_mlp_precision; `state` is what hip_backward needs
         (None when no gradient is wanted).  live_only: the colour of a sample without density, other than a ray's last, may come
-        back as 0.0 (ops.mlp_fwd_live) -- for a caller that integrates `raw` without noise; needs ops.live_colour_kernel(FAMILY)."""
+        back as 0.0 (ops.mlp_fwd_live) -- for a caller that integrates `raw` without noise; needs ops.live_colour_kernel(FAMILY).
+        live_only="gated": such a sample may, besides, come back with ANY NEGATIVE density in place of its own (ops.mlp_fwd_gated:
+        fc_feat is skipped where a bound proves the density negative) -- the same caller, the same outputs of the integrator."""
         ops.check_conditioning(expr, latent)
         fam, hw, prec = self.FAMILY, self.hip_weights(), ops.get_mlp_precision()
         fam.require_precision(prec)
@@ -43,6 +45,8 @@ class _FusedNeRFModel(torch.nn.Module):
             if need_grad or not ops.live_colour_kernel(fam):
                 raise ValueError("live_only is an exact-f32 inference option of the families in ops.LIVE_FAMILIES (ops.live_colour_kernel)")
             packed = hw.get()
+            if live_only == "gated":
+                return ops.mlp_fwd_gated(fam, packed, hw.get_bound(), ops.mlp_condition(fam, packed, expr, latent, near, far), ro, rd, z, rd_view), None
             return ops.mlp_fwd_live(fam, packed, ops.mlp_condition(fam, packed, expr, latent, near, far), ro, rd, z, rd_view), None
         packed = hw.get()
         cond = ops.mlp_condition(fam, packed, expr, latent, near, far)

@@ -335,6 +335,16 @@ class MLPWeights:
     def get(self) -> torch.Tensor:
         return self._get("f32")
 
+    def get_bound(self) -> torch.Tensor:
+        """The sigma-bound image of get() (csrc/nf_mlp_gated.hip): built from the f32 image by one small kernel, cached under that
+        image's signature and so rebuilt exactly when the image is."""
+        packed = self._get("f32")
+        sig = self._cache["f32"][0]
+        hit = self._cache.get("bound")
+        if hit is None or hit[0] != sig or hit[1].device != packed.device:
+            self._cache["bound"] = hit = (sig, sigma_bound(self.family, packed))
+        return hit[1]
+
     def get_t(self) -> torch.Tensor:
         return self._get("f32_t")
 
@@ -426,9 +436,12 @@ def live_rotation_step(workgroups: int) -> int:
 
 
 def set_live_colour(on, passes=("coarse", "fine")) -> None:
-    """on=True: the passes named take the kernel; on=False: none does; on=None: back to LIVE_PASSES_DEFAULT."""
-    global _live_passes
+    """on=True: the passes named take the kernel; on=False: none does; on=None: back to LIVE_PASSES_DEFAULT.  An explicit choice
+    (True / False) is a choice of THIS kernel or of the full one: no pass takes the gated kernel (set_sigma_gate) until it is
+    switched on again; None restores that kernel's default passes too."""
+    global _live_passes, _gated_passes
     _live_passes = set(LIVE_PASSES_DEFAULT) if on is None else (set(passes) if on else set())
+    _gated_passes = set(GATED_PASSES_DEFAULT) if on is None else set()
 
 
 def live_colour_kernel(fam: MLPFamily) -> bool:
@@ -483,6 +496,94 @@ def mlp_fwd_live_stats(fam: MLPFamily, packed, cond, ro, rd, z, rd_view=None, ma
         stats = torch.empty((waves, len(LIVE_STAT_COLUMNS)), dtype=torch.int64, device=dev)
         fam.call("mlp_fwd_live_stats", H.ptr(packed), H.ptr(cond), H.ptr(ro), H.ptr(rd), H.ptr(rd_view), H.ptr(z), n_rays, n_samples,
                  H.ptr(raw), H.ptr(scratch), scratch.numel(), int(max_workgroups), stats.data_ptr(), waves, H.stream_ptr(dev))
+    return raw, stats
+
+
+# fc_feat, too, only where it is needed (csrc/nf_mlp_gated.hip): the live-colour kernel with the trunk ended behind layers_xyz.5.  A
+# bound on the density, a 256-term dot product on relu(layers_xyz.5) (DESIGN.md "Sigma gate"), proves most samples without density
+# dead; fc_feat, fc_alpha and the colour layers run on the others.  Against mlp_fwd: all four channels bit for bit where
+# !(sigma <= 0) or on a ray's last sample; elsewhere rgb 0.0 and sigma either mlp_fwd's or SOME NEGATIVE NUMBER -- so, again,
+# volume_render_fwd without noise gives the same outputs bit for bit.  A pass in GATED_PASSES_DEFAULT takes this kernel in front of
+# the live-colour one; the default is what measured faster than the live kernel on every frame (profiles/sigma_gate.md).
+GATED_PASSES_DEFAULT = ("coarse",)      # coarse (kept 0.27 .. 0.58): -1.1 .. -2.3 ms of 26 ms; fine (kept 0.75 .. 0.89): within its spread
+# NERFACE_SIGMA_GATE="coarse,fine" (or one of them, or "") sets the passes for a process whose code one does not edit (bench.py)
+_gated_passes = (set(GATED_PASSES_DEFAULT) if os.environ.get("NERFACE_SIGMA_GATE") is None
+                 else {p for p in os.environ["NERFACE_SIGMA_GATE"].split(",") if p in ("coarse", "fine")})
+_gated_launches = [0]
+GATED_STAT_COLUMNS = LIVE_STAT_COLUMNS + ("proven_rows",)
+
+
+def set_sigma_gate(on, passes=("coarse", "fine")) -> None:
+    """on=True: the passes named take the gated kernel; on=False: none does; on=None: back to GATED_PASSES_DEFAULT."""
+    global _gated_passes
+    _gated_passes = set(GATED_PASSES_DEFAULT) if on is None else (set(passes) if on else set())
+
+
+def sigma_gate_applies(fam: MLPFamily, which: str) -> bool:
+    """Pass `which` of a render without noise takes the gated kernel: switched on for it, under live_colour_kernel's conditions."""
+    return which in _gated_passes and live_colour_kernel(fam)
+
+
+def live_mode(fam: MLPFamily, which: str):
+    """What a pass `which` without noise and without gradient passes to hip_forward(live_only=...): "gated", True (live) or False."""
+    if sigma_gate_applies(fam, which):
+        return "gated"
+    return live_colour_applies(fam, which)
+
+
+def sigma_gate_launches() -> int:
+    return _gated_launches[0]
+
+
+def sigma_bound(fam: MLPFamily, packed) -> torch.Tensor:
+    """The sigma-bound image of the packed f32 image `packed` (MLPWeights.get_bound() caches it beside the image)."""
+    if fam.prefix not in LIVE_FAMILIES:
+        raise NotImplementedError(f"the {fam.prefix} model family has no gated kernel")
+    dev = H.require_device(packed)
+    bound = torch.empty(fam.fn("sigma_bound_floats")(), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        fam.call("sigma_bound", H.ptr(packed), H.ptr(bound), H.stream_ptr(dev))
+    return bound
+
+
+def _gated_call(entry, fam, packed, bound, cond, ro, rd, z, rd_view, max_workgroups, scratch, raw, *tail):
+    n_rays, n_samples = z.shape
+    fam.call(entry, H.ptr(packed), H.ptr(bound), H.ptr(cond), H.ptr(ro), H.ptr(rd), H.ptr(rd_view), H.ptr(z), n_rays, n_samples, H.ptr(raw),
+             H.ptr(scratch), scratch.numel(), int(max_workgroups), *tail)
+
+
+def mlp_fwd_gated(fam: MLPFamily, packed, bound, cond, ro, rd, z, rd_view=None, max_workgroups: int = 0) -> torch.Tensor:
+    """mlp_fwd_live with fc_feat, too, only on the samples `bound` (sigma_bound(fam, packed)) cannot prove dead (see above) ->
+    raw (n_rays, n_samples, 4)."""
+    if fam.prefix not in LIVE_FAMILIES:
+        raise NotImplementedError(f"the {fam.prefix} model family has no gated kernel")
+    dev = H.require_device(packed, bound, cond, ro, rd, z, rd_view)
+    n_rays, n_samples = z.shape
+    raw = torch.empty((n_rays, n_samples, 4), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        key = (dev, H.stream_ptr(dev), int(max_workgroups))
+        scratch = _LIVE_SCRATCH.get(key)
+        if scratch is None:
+            scratch = _LIVE_SCRATCH[key] = torch.empty(fam.fn("mlp_fwd_live_scratch_floats")(int(max_workgroups)), dtype=torch.float32, device=dev)
+        _gated_call("mlp_fwd_gated", fam, packed, bound, cond, ro, rd, z, rd_view, max_workgroups, scratch, raw, H.stream_ptr(dev))
+    _gated_launches[0] += 1
+    return raw
+
+
+def mlp_fwd_gated_stats(fam: MLPFamily, packed, bound, cond, ro, rd, z, rd_view=None, max_workgroups: int = 0):
+    """mlp_fwd_gated through the kernel's statistics instantiation -> (raw, stats): stats is int64 (waves, 5) in the order of
+    GATED_STAT_COLUMNS (mlp_fwd_live_stats' columns, a gathered run counting as a colour run, and the rows the wave proved dead)."""
+    if fam.prefix not in LIVE_FAMILIES:
+        raise NotImplementedError(f"the {fam.prefix} model family has no gated kernel")
+    dev = H.require_device(packed, bound, cond, ro, rd, z, rd_view)
+    n_rays, n_samples = z.shape
+    raw = torch.empty((n_rays, n_samples, 4), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        scratch = torch.empty(fam.fn("mlp_fwd_live_scratch_floats")(int(max_workgroups)), dtype=torch.float32, device=dev)
+        waves = scratch.numel() * 4 // (LIVE_RING_ROWS * LIVE_ROW_BYTES)
+        stats = torch.empty((waves, len(GATED_STAT_COLUMNS)), dtype=torch.int64, device=dev)
+        _gated_call("mlp_fwd_gated_stats", fam, packed, bound, cond, ro, rd, z, rd_view, max_workgroups, scratch, raw, stats.data_ptr(), waves,
+                    H.stream_ptr(dev))
     return raw, stats
 
 

@@ -81,8 +81,9 @@ class _RenderChunk(torch.autograd.Function):
         lat_d = latent.detach().reshape(-1).contiguous()
         # a pass integrated without noise never sees the colour of a sample without density (alpha = 0 exactly): the exact-f32
         # inference kernel that skips the colour layers there serves it (ops.mlp_fwd_live); every other pass takes the full forward
-        live_c = not need_grad and noise_c is None and ops.live_colour_applies(model_c.FAMILY, "coarse")
-        live_f = not need_grad and noise_f is None and model_f is not None and ops.live_colour_applies(model_f.FAMILY, "fine")
+        # (ops.live_mode: the gated kernel, which also skips fc_feat where it can prove the density negative, then the live one)
+        live_c = not need_grad and noise_c is None and ops.live_mode(model_c.FAMILY, "coarse")
+        live_f = not need_grad and noise_f is None and model_f is not None and ops.live_mode(model_f.FAMILY, "fine")
         z_c = ops.sample_coarse(n_rays, nc, near, far, dev, t_rand, lindisp=cfg["lindisp"])
         if cfg.get("coarse_density_only"):
             # colour-free coarse pass (inference with a fine network): the coarse weights, disparity and acc depend on the density

@@ -636,6 +636,25 @@ int nf_paper_mlp_fwd_live_stats(const float* packed, const float* cond, const fl
                                 const float* z, int64_t n_rays, int n_samples, float* raw, float* scratch, size_t scratch_floats,
                                 int max_workgroups, int64_t* stats, size_t stats_rows, nf_stream_t stream);
 
+/* ---- fc_feat, too, only where it is needed (ABI 5 still: these only add) ------------------------------------------------------------
+ * nf_paper_mlp_fwd_gated: nf_paper_mlp_fwd_live with the trunk ended behind layers_xyz.5.  A 256-term dot product on
+ * relu(layers_xyz.5) and a rounding bound (DESIGN.md "Sigma gate") prove most samples without density dead; fc_feat and everything
+ * behind it run on the others only.  Per point, against nf_paper_mlp_fwd: where !(sigma_raw <= 0), or on a ray's last sample, all four
+ * channels are the same bits; elsewhere rgb is 0.0 and sigma_raw is either the same bits or some negative number (never NaN).
+ * nf_volume_render_fwd WITHOUT a noise tensor gives the same outputs from either `raw`.
+ * bound: nf_paper_sigma_bound_floats() floats, 16-byte aligned, written by nf_paper_sigma_bound(packed, bound, stream) from the image
+ * nf_paper_pack wrote: it is valid for that image, and `cond` must be a bias table of that image.  scratch, max_workgroups, the unit
+ * counters: as nf_paper_mlp_fwd_live.  nf_paper_mlp_fwd_gated_stats: stats is int64 [stats_rows][5], nf_paper_mlp_fwd_live_stats' four
+ * columns (a "colour run" is a gathered run) and the rows the wave proved dead.                                                     */
+size_t nf_paper_sigma_bound_floats(void);
+int nf_paper_sigma_bound(const float* packed, float* bound, nf_stream_t stream);
+int nf_paper_mlp_fwd_gated(const float* packed, const float* bound, const float* cond, const float* ro, const float* rd,
+                           const float* rd_view, const float* z, int64_t n_rays, int n_samples, float* raw, float* scratch,
+                           size_t scratch_floats, int max_workgroups, nf_stream_t stream);
+int nf_paper_mlp_fwd_gated_stats(const float* packed, const float* bound, const float* cond, const float* ro, const float* rd,
+                                 const float* rd_view, const float* z, int64_t n_rays, int n_samples, float* raw, float* scratch,
+                                 size_t scratch_floats, int max_workgroups, int64_t* stats, size_t stats_rows, nf_stream_t stream);
+
 /* ---- isosurface of a dense grid (ABI 5 still: these only add) ------------------------------------------------------------------
  * grid: float32 [nz][ny][nx], x fastest; every axis n >= 2.  Marching tetrahedra on the Kuhn triangulation (DESIGN.md
  * "Isosurface" is the specification): a welded, consistently oriented mesh, normals from inside (v > level) to outside; vertex ids
