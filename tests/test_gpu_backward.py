@@ -60,10 +60,15 @@ def relu_masks(sv, n_points, mode):
     -- not the sign of the (hi, lo) pair, which is 0 for a positive activation below the pair's underflow (fp16: 1.9e-9)."""
     if mode in ("f32", False, None):
         return [saved_section(sv, k, n_points) > 0 for k in RELU_ORDER]
-    words = sv[2256 * n_points:(2256 + 72) * n_points].view(torch.int32).view(9, n_points, 2, 4)
+    return bit_masks(sv, n_points, 2256, [SAVED[k][1] for k in RELU_ORDER])
+
+
+def bit_masks(sv, n_points, off, widths):
+    """The bit masks of a split forward's mask section (layout above) that starts `off` floats per point into the f32-row form of
+    `saved`, one layer per entry of `widths`."""
+    words = sv[off * n_points:(off + 8 * len(widths)) * n_points].view(torch.int32).view(len(widths), n_points, 2, 4)
     out = []
-    for l, k in enumerate(RELU_ORDER):
-        width = SAVED[k][1]
+    for l, width in enumerate(widths):
         m = torch.zeros((n_points, width), dtype=torch.bool, device=sv.device)
         for nt in range(width // 32):
             for h in range(2):
@@ -513,7 +518,8 @@ def test_training_kernels_vs_fp64_at_training_size(hip_lib, gpu, n_rays, s, spre
 def test_split_dw_gemm_matches_exact_at_training_size(hip_lib, gpu, n_rays, s):
     """BASELINE training sizes (configs[2]: 2048 rays, 64 coarse / 128 fine samples; plus a ragged size whose last
     16-point stage is partial): on the SAME saved activations and dZ, the split-bf16 weight-gradient kernel (one 16-wave
-    workgroup per CU) must agree with the exact-f32 one (28 slices) to the split's 2^-16 class, tensor by tensor."""
+    workgroup per CU) must agree with the exact-f32 one (the per-group slice plan of nf_dw_plan_groups: on 256 CUs 30 slices per
+    group of four full products, 15 for the products against the positional encoding) to the split's 2^-16 class, tensor by tensor."""
     import nerf
     from nerf import ops
     c = C.build_case("train_rand_64_64")
