@@ -108,20 +108,62 @@ struct NfGatePre {
 #define NF_LIVE_STAT_RUNS 1                               // colour runs, the final flush included
 #define NF_LIVE_STAT_FLUSH 2                              // rows of the final flush
 #define NF_LIVE_STAT_CLOCK 3                              // wall_clock64() at exit
-#define NF_LIVE_STAT_COLS 4
 #define NF_GATE_STAT_PROVEN 4                             // GATE: rows proven dead (a fifth column; the first four as above, "colour run" =
-#define NF_GATE_STAT_COLS 5                               // gathered run)
+                                                          // gathered run)
+// On request (nf_live_launch's `clocks`: the row is then NF_LIVE_PHASES columns longer) six columns of shader clocks (s_memtime) follow,
+// summed over the wave's passes: where a pass spends its time.  The request rides in bit 0 of the kernel's `stats` pointer, which is
+// 8-byte aligned: the STATS instantiations alone look at it, and the entry points with the short rows keep their layout.
+#define NF_LIVE_PH_TRUNK 0                                // a unit's inputs and the trunk up to the hook (NfLivePre / NfGatePre::wait())
+#define NF_LIVE_PH_TILE 1                                 // the hook and the lone tile
+#define NF_LIVE_PH_APPEND 2                               // ballot and append
+#define NF_LIVE_PH_ENTRY 3                                // a run's gathers and slab fills, up to its first MFMA
+#define NF_LIVE_PH_RUN 4                                  // the run and its stores
+#define NF_LIVE_PH_DEAD 5                                 // the stores of the rows finished without a colour
+#define NF_LIVE_PHASES 6
+#define NF_LIVE_STAT_COLS 4
+#define NF_GATE_STAT_COLS 5
 
 // one lane of the wave adds to its row; the row belongs to the wave, and nothing is held in a register across the trunk
 template <bool STATS, int COLS = NF_LIVE_STAT_COLS>
 __device__ __forceinline__ void nf_live_stat(long long* stats, int col, long long add, bool set = false) {
     if constexpr (STATS) {
+        const int cols = COLS + (((uintptr_t)stats & 1) ? NF_LIVE_PHASES : 0);
+        stats = reinterpret_cast<long long*>((uintptr_t)stats & ~(uintptr_t)7);
         if ((threadIdx.x & 63) == 0) {
-            long long* at = stats + ((size_t)blockIdx.x * NF_MLP_WAVES + (threadIdx.x >> 6)) * COLS + col;
-            *at = set ? add : *at + add;
+            long long* at = stats + ((size_t)blockIdx.x * NF_MLP_WAVES + (threadIdx.x >> 6)) * cols + col;
+            if (set) *at = add;                           // (an add that returns nothing: no load, no wait for it in the middle of a pass)
+            else (void)__hip_atomic_fetch_add(at, add, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     }
 }
+
+// STATS: one reading of the shader clock ends phase `end` and starts phase `start` (NF_LIVE_PH_*, -1: none).  A phase's column is the
+// sum of its ends minus the sum of its starts, so a mark is two adds that return nothing: no load, no wait, no register kept.
+template <bool STATS, int COLS>
+__device__ __forceinline__ void nf_live_mark(long long* stats, int end, int start) {
+    if constexpr (STATS) {
+        if ((uintptr_t)stats & 1) {
+            __builtin_amdgcn_sched_barrier(0);
+            const long long t = (long long)__builtin_amdgcn_s_memtime();
+            if ((threadIdx.x & 63) == 0) {
+                long long* row = reinterpret_cast<long long*>((uintptr_t)stats & ~(uintptr_t)7) +
+                                 ((size_t)blockIdx.x * NF_MLP_WAVES + (threadIdx.x >> 6)) * (COLS + NF_LIVE_PHASES) + COLS;
+                if (end >= 0) (void)__hip_atomic_fetch_add(row + end, t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (start >= 0) (void)__hip_atomic_fetch_add(row + start, -t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+}
+// the hooks of the STATS instantiations: the same requests, behind a mark where the trunk ends
+template <class Pre, int COLS>
+struct NfMarkedPre : Pre {
+    long long* stats;
+    __device__ __forceinline__ void wait() const {
+        nf_live_mark<true, COLS>(stats, NF_LIVE_PH_TRUNK, NF_LIVE_PH_TILE);
+        Pre::wait();
+    }
+};
 
 // GATE: the kernel of nf_mlp_gated.hip; `bound` is the sigma-bound image of `packed` (not read otherwise).
 template <int NT, bool STATS, bool GATE = false>
@@ -186,21 +228,30 @@ k_paper_mlp_fwd_live(const float* __restrict__ packed, const float* __restrict__
         bool proven[NT] = {};
         int live_v = 0, run_v = 0;                        // the pass's 32-bit liveness mask; nonzero: the colour layers run
         if (more) {
+            nf_live_mark<STATS, COLS>(stats, -1, NF_LIVE_PH_TRUNK);
             f32x4 pe[NT][4];
             nf_net_inputs<NT>(pe, dirf, p0, n_points, S, lane, ro, rd, rdv_v, z_v);
             f32x4 acc[NT][16];
             if constexpr (GATE) {
-                nf_paper_net_body<Net, NT, 1, true, NfGatePre, true>(acc, sigma_own, pe, dirf, Wi, Ci, act4, lane,
-                                                                     NfGatePre{st, pf, ring_v, head_v, tail_v, bound_v});
+                if constexpr (STATS)
+                    nf_paper_net_body<Net, NT, 1, true, NfMarkedPre<NfGatePre, COLS>, true>(
+                        acc, sigma_own, pe, dirf, Wi, Ci, act4, lane, NfMarkedPre<NfGatePre, COLS>{{st, pf, ring_v, head_v, tail_v, bound_v}, stats});
+                else
+                    nf_paper_net_body<Net, NT, 1, true, NfGatePre, true>(acc, sigma_own, pe, dirf, Wi, Ci, act4, lane,
+                                                                         NfGatePre{st, pf, ring_v, head_v, tail_v, bound_v});
 #pragma unroll
                 for (int t = 0; t < NT; ++t) {             // proven dead iff s + 2^-13 u < -2^-100, false for NaN or infinite operands
                     const float s = acc[t][8].x, u = acc[t][8].y;
                     sigma_own[t] = nf_add(s, nf_mul(u, 0x1p-13f));
                     proven[t] = sigma_own[t] < -0x1p-100f && s > -INFINITY && u < INFINITY;
                 }
+            } else if constexpr (STATS) {
+                nf_paper_net_body<Net, NT, 1, true>(acc, sigma_own, pe, dirf, Wi, Ci, act4, lane,
+                                                    NfMarkedPre<NfLivePre, COLS>{{st, wd, pf, ring_v, head_v, tail_v}, stats});
             } else {
                 nf_paper_net_body<Net, NT, 1, true>(acc, sigma_own, pe, dirf, Wi, Ci, act4, lane, NfLivePre{st, wd, pf, ring_v, head_v, tail_v});
             }
+            nf_live_mark<STATS, COLS>(stats, NF_LIVE_PH_TILE, NF_LIVE_PH_APPEND);
             int lane_o = lane;
             asm volatile("" : "+v"(lane_o));
             const int g = lane_o >> 4, c = lane_o & 15;
@@ -213,8 +264,14 @@ k_paper_mlp_fwd_live(const float* __restrict__ packed, const float* __restrict__
 #pragma unroll
             for (int t = 0; t < NT; ++t) {
                 const int64_t p = p0_o + 16 * t + c;
-                const bool is_live = g == 0 && p < n_points && ((GATE ? !proven[t] : !(sigma_own[t] <= 0.0f)) || (p + 1) % S_o == 0);
-                if constexpr (GATE) tag_own[t] = __int_as_float((p + 1) % S_o == 0 ? 1 : 0);
+                bool is_live;
+                if constexpr (GATE) {                     // (the 64-bit remainder once: it is some 300 clocks of vector work per tile)
+                    const bool last = (p + 1) % S_o == 0;
+                    is_live = g == 0 && p < n_points && (!proven[t] || last);
+                    tag_own[t] = __int_as_float(last ? 1 : 0);
+                } else {
+                    is_live = g == 0 && p < n_points && (!(sigma_own[t] <= 0.0f) || (p + 1) % S_o == 0);
+                }
                 live |= ((unsigned)__builtin_amdgcn_ballot_w64(is_live) & 0xffffu) << (16 * t);
             }
             const int head = __builtin_amdgcn_readfirstlane(head_v), cnt = head - __builtin_amdgcn_readfirstlane(tail_v);
@@ -259,6 +316,7 @@ k_paper_mlp_fwd_live(const float* __restrict__ packed, const float* __restrict__
                 head_v = head + n_live;
                 asm volatile("" : "+v"(head_v));
             }
+            nf_live_mark<STATS, COLS>(stats, NF_LIVE_PH_APPEND, -1);
         } else {
             // behind the wave's last block: what the ring holds goes to rows 0 .. R - 1 of the slab.  (The requests are made with an
             // empty ring too, once per wave: every path into the colour run below defines what it reads.)
@@ -283,6 +341,7 @@ k_paper_mlp_fwd_live(const float* __restrict__ packed, const float* __restrict__
         if (run != 0) {
             nf_live_stat<STATS, COLS>(stats, NF_LIVE_STAT_RUNS, 1);
             if (run == 2) nf_live_stat<STATS, COLS>(stats, NF_LIVE_STAT_FLUSH, __builtin_amdgcn_readfirstlane(head_v) - __builtin_amdgcn_readfirstlane(tail_v));
+            nf_live_mark<STATS, COLS>(stats, -1, NF_LIVE_PH_ENTRY);
             int lane_o = lane;
             asm volatile("" : "+v"(lane_o));
             const int g = lane_o >> 4, c = lane_o & 15;
@@ -336,6 +395,7 @@ k_paper_mlp_fwd_live(const float* __restrict__ packed, const float* __restrict__
             constexpr int NDIR = 1;
             constexpr unsigned D0 = Net::OFF_D0 / 4;
             nf_read_b<NT>(st.b0, act4, lane, 0);
+            nf_live_mark<STATS, COLS>(stats, NF_LIVE_PH_ENTRY, NF_LIVE_PH_RUN);
             f32x4 acc[NT][16], bj[NT];
             float sigma_raw[NT];
             if constexpr (GATE) {
@@ -366,10 +426,12 @@ k_paper_mlp_fwd_live(const float* __restrict__ packed, const float* __restrict__
             }
             tail_v = tail + n_fill;
             asm volatile("" : "+v"(tail_v));
+            nf_live_mark<STATS, COLS>(stats, NF_LIVE_PH_RUN, -1);
         }
         asm volatile("" : "+v"(more_v));
         if (__builtin_amdgcn_readfirstlane(more_v) == 0) break;
         {   // the dead points of the block: finished without a colour
+            nf_live_mark<STATS, COLS>(stats, -1, NF_LIVE_PH_DEAD);
             int lane_s = lane;
             asm volatile("" : "+v"(lane_s));
             const int g = lane_s >> 4, c = lane_s & 15;
@@ -379,6 +441,7 @@ k_paper_mlp_fwd_live(const float* __restrict__ packed, const float* __restrict__
                 const int64_t p = p0_v + 16 * t + c;
                 if (g == 0 && p < n_points && !(((unsigned)live_v >> (16 * t + c)) & 1u)) raw_v[p] = (f32x4){0.0f, 0.0f, 0.0f, sigma_own[t]};
             }
+            nf_live_mark<STATS, COLS>(stats, NF_LIVE_PH_DEAD, -1);
         }
         asm volatile("" : "+v"(next_v));
         unit_v = next_v;
@@ -443,13 +506,14 @@ inline unsigned* nf_live_counter(hipStream_t stream) {
 template <bool STATS, bool GATE = false>
 static inline int nf_live_launch(const float* packed, const float* cond, const float* ro, const float* rd, const float* rd_view, const float* z,
                                  int64_t n_rays, int n_samples, float* raw, float* scratch, size_t scratch_floats, int max_workgroups,
-                                 long long* stats, nf_stream_t stream, const float* bound = nullptr) {
+                                 long long* stats, nf_stream_t stream, const float* bound = nullptr, bool clocks = false) {
     static_assert(NF_MLP_WAVES * 16 * NF_MLP_NT == 128, "nf_mlp_fwd_launch sizes the grid for 128 points per workgroup");
     if (max_workgroups < 0 || !scratch || ((uintptr_t)scratch & 15) ||
         scratch_floats < (size_t)nf_live_grid_cap(max_workgroups) * NF_MLP_WAVES * (NF_LIVE_WAVE_B / 4) ||
         (GATE && (!bound || ((uintptr_t)bound & 15))))
         return NF_EINVAL;
     const float* rdv = rd_view ? rd_view : rd;
+    if (STATS && clocks) stats = reinterpret_cast<long long*>((uintptr_t)stats | 1);      // (a request for the clock columns: see NF_LIVE_PH_*)
     int rc = 0;
     const int launched = nf_mlp_fwd_launch(NF_FWD_INFER, packed, cond, ro, rd, z, raw, nullptr, n_rays, n_samples, [&](int64_t n_points, unsigned grid) {
         if ((n_points + 31) / 32 > ((int64_t)1 << 31)) {

@@ -278,7 +278,47 @@ __device__ __forceinline__ void nf_net_lone_tile(f32x4 (&acc)[NT][16], const NfS
     pre.wait();
 #pragma unroll
     for (int ch = 1; ch < 16; ++ch) w8[ch] = nf_load_w1(W, first4 + stride4 * ch, lane);
+    if constexpr (RELU_IN) __builtin_amdgcn_sched_barrier(0);     // (the tile's own weights come back first: loads return in order)
     pre.loads(Wi, Ci, lane);
+    if constexpr (RELU_IN) {
+        // (GATE only.)  With two MFMA chains in flight nothing hides a chunk's LDS read or its eight v_max if they stand between two
+        // chunks, as the plain order below leaves them (profiles/sigma_gate_fine.md: 2,500 clocks per pass against the tile without
+        // ReLU).  So chunk ch + 1 is read in front of chunk ch's MFMAs and its ReLU is dealt out among the chunk's last four.  The
+        // MFMAs, their operands and their order per accumulator are the plain loop's.
+        f32x4 cur[NT], nxt[NT];
+#pragma unroll
+        for (int t = 0; t < NT; ++t) cur[t] = nf_relu_i(st.b0[t]);
+#pragma unroll
+        for (int ch = 0; ch < 16; ++ch) {
+            if (ch + 1 < 16) nf_read_b<NT>(nxt, act4, lane, ch + 1);
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int r = 0; r < 2; ++r)
+#pragma unroll
+                for (int t = 0; t < NT; ++t)
+                    acc[t][8] = __builtin_amdgcn_mfma_f32_16x16x4f32(w8[ch][r], cur[t][r], (ch == 0 && r == 0) ? st.bias[0] : acc[t][8], 0, 0, 0);
+#pragma unroll
+            for (int r = 2; r < 4; ++r)
+#pragma unroll
+                for (int t = 0; t < NT; ++t) {
+                    __builtin_amdgcn_sched_barrier(0);
+                    if (ch + 1 < 16) {
+                        const int e = 2 * (r - 2);         // two of the next fragment's four values per MFMA
+#pragma unroll
+                        for (int q = e; q < e + 2; ++q) {
+                            const int xi = __float_as_int(nxt[t][q]);
+                            nxt[t][q] = __int_as_float(xi > 0 ? xi : 0);                 // v_max_i32, as nf_relu_i
+                        }
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+                    acc[t][8] = __builtin_amdgcn_mfma_f32_16x16x4f32(w8[ch][r], cur[t][r], acc[t][8], 0, 0, 0);
+                }
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int t = 0; t < NT; ++t) cur[t] = nxt[t];
+        }
+        return;
+    }
 #pragma unroll
     for (int ch = 0; ch < 16; ++ch) {
         if (ch == 0) {

@@ -199,7 +199,10 @@ _PROTOTYPES["nf_paper_mlp_fwd_live_stats"] = (C.c_int, [_P, _P, _P, _P, _P, _P, 
 _PROTOTYPES["nf_paper_sigma_bound_floats"] = (_Z, [])
 _PROTOTYPES["nf_paper_sigma_bound"] = (C.c_int, [_P, _P, _P])
 _PROTOTYPES["nf_paper_mlp_fwd_gated"] = (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _L, _I, _P, _P, _Z, _I, _P])
+# the statistics instantiations with the clocks of a pass's phases behind each row (rows of 4 + 6 and 5 + 6 int64)
+_PROTOTYPES["nf_paper_mlp_fwd_live_phases"] = _PROTOTYPES["nf_paper_mlp_fwd_live_stats"]
 _PROTOTYPES["nf_paper_mlp_fwd_gated_stats"] = (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _L, _I, _P, _P, _Z, _I, _P, _Z, _P])
+_PROTOTYPES["nf_paper_mlp_fwd_gated_phases"] = _PROTOTYPES["nf_paper_mlp_fwd_gated_stats"]
 # isosurface of a dense grid: count (workspace, V and F on the device), then emit (lo / hi are host float[3])
 _PROTOTYPES["nf_isosurface_workspace_bytes"] = (_Z, [_I, _I, _I])
 _PROTOTYPES["nf_isosurface_count"] = (C.c_int, [_P, _I, _I, _I, _F, _P, _Z, _P, _P])

@@ -477,13 +477,15 @@ def mlp_fwd_live(fam: MLPFamily, packed, cond, ro, rd, z, rd_view=None, max_work
     return raw
 
 
-LIVE_STAT_COLUMNS = ("units", "colour_runs", "flush_rows", "exit_clock")
+# what a wave did, then where its passes spent their shader clocks (sums over the wave's passes; csrc/nf_mlp_live_kernel.h, nf_live_mark)
+LIVE_PHASE_COLUMNS = ("clk_trunk", "clk_lone_tile", "clk_append", "clk_run_entry", "clk_run", "clk_dead_stores")
+LIVE_STAT_COLUMNS = ("units", "colour_runs", "flush_rows", "exit_clock") + LIVE_PHASE_COLUMNS
 
 
 def mlp_fwd_live_stats(fam: MLPFamily, packed, cond, ro, rd, z, rd_view=None, max_workgroups: int = 0):
     """mlp_fwd_live through the kernel's statistics instantiation (csrc/nf_mlp_live_stats.hip) -> (raw, stats): stats is int64
-    (waves, 4) in the order of LIVE_STAT_COLUMNS, one row per wave of the capped grid (workgroup * 4 + wave; rows of workgroups the
-    launch did not start stay zero); exit_clock is the device's wall_clock64() when the wave left.  An instrument for tests and
+    (waves, 10) in the order of LIVE_STAT_COLUMNS, one row per wave of the capped grid (workgroup * 4 + wave; rows of workgroups the
+    launch did not start stay zero); exit_clock is the device's wall_clock64() when the wave left, the clk_ columns are shader clocks.  An instrument for tests and
     profiles (tools/live_schedule_sim.py); no render path calls it."""
     if fam.prefix not in LIVE_FAMILIES:
         raise NotImplementedError(f"the {fam.prefix} model family has no live-colour kernel")
@@ -494,7 +496,7 @@ def mlp_fwd_live_stats(fam: MLPFamily, packed, cond, ro, rd, z, rd_view=None, ma
         scratch = torch.empty(fam.fn("mlp_fwd_live_scratch_floats")(int(max_workgroups)), dtype=torch.float32, device=dev)
         waves = scratch.numel() * 4 // (LIVE_RING_ROWS * LIVE_ROW_BYTES)
         stats = torch.empty((waves, len(LIVE_STAT_COLUMNS)), dtype=torch.int64, device=dev)
-        fam.call("mlp_fwd_live_stats", H.ptr(packed), H.ptr(cond), H.ptr(ro), H.ptr(rd), H.ptr(rd_view), H.ptr(z), n_rays, n_samples,
+        fam.call("mlp_fwd_live_phases", H.ptr(packed), H.ptr(cond), H.ptr(ro), H.ptr(rd), H.ptr(rd_view), H.ptr(z), n_rays, n_samples,
                  H.ptr(raw), H.ptr(scratch), scratch.numel(), int(max_workgroups), stats.data_ptr(), waves, H.stream_ptr(dev))
     return raw, stats
 
@@ -504,13 +506,14 @@ def mlp_fwd_live_stats(fam: MLPFamily, packed, cond, ro, rd, z, rd_view=None, ma
 # dead; fc_feat, fc_alpha and the colour layers run on the others.  Against mlp_fwd: all four channels bit for bit where
 # !(sigma <= 0) or on a ray's last sample; elsewhere rgb 0.0 and sigma either mlp_fwd's or SOME NEGATIVE NUMBER -- so, again,
 # volume_render_fwd without noise gives the same outputs bit for bit.  A pass in GATED_PASSES_DEFAULT takes this kernel in front of
-# the live-colour one; the default is what measured faster than the live kernel on every frame (profiles/sigma_gate.md).
-GATED_PASSES_DEFAULT = ("coarse",)      # coarse (kept 0.27 .. 0.58): -1.1 .. -2.3 ms of 26 ms; fine (kept 0.75 .. 0.89): within its spread
+# the live-colour one; the default is what measured faster than the live kernel on every frame, by more than that kernel's own spread.
+# (profiles/sigma_gate_fine.md) coarse (kept 0.27 .. 0.58): -1.2 .. -2.4 ms of 26 ms; fine (kept 0.75 .. 0.89): -0.26 .. -1.77 ms of 83 ms
+GATED_PASSES_DEFAULT = ("coarse", "fine")
 # NERFACE_SIGMA_GATE="coarse,fine" (or one of them, or "") sets the passes for a process whose code one does not edit (bench.py)
 _gated_passes = (set(GATED_PASSES_DEFAULT) if os.environ.get("NERFACE_SIGMA_GATE") is None
                  else {p for p in os.environ["NERFACE_SIGMA_GATE"].split(",") if p in ("coarse", "fine")})
 _gated_launches = [0]
-GATED_STAT_COLUMNS = LIVE_STAT_COLUMNS + ("proven_rows",)
+GATED_STAT_COLUMNS = LIVE_STAT_COLUMNS[:4] + ("proven_rows",) + LIVE_PHASE_COLUMNS
 
 
 def set_sigma_gate(on, passes=("coarse", "fine")) -> None:
@@ -571,8 +574,9 @@ def mlp_fwd_gated(fam: MLPFamily, packed, bound, cond, ro, rd, z, rd_view=None, 
 
 
 def mlp_fwd_gated_stats(fam: MLPFamily, packed, bound, cond, ro, rd, z, rd_view=None, max_workgroups: int = 0):
-    """mlp_fwd_gated through the kernel's statistics instantiation -> (raw, stats): stats is int64 (waves, 5) in the order of
-    GATED_STAT_COLUMNS (mlp_fwd_live_stats' columns, a gathered run counting as a colour run, and the rows the wave proved dead)."""
+    """mlp_fwd_gated through the kernel's statistics instantiation -> (raw, stats): stats is int64 (waves, 11) in the order of
+    GATED_STAT_COLUMNS (mlp_fwd_live_stats' columns, a gathered run counting as a colour run, with the rows the wave proved dead in
+    front of the clocks)."""
     if fam.prefix not in LIVE_FAMILIES:
         raise NotImplementedError(f"the {fam.prefix} model family has no gated kernel")
     dev = H.require_device(packed, bound, cond, ro, rd, z, rd_view)
@@ -582,7 +586,7 @@ def mlp_fwd_gated_stats(fam: MLPFamily, packed, bound, cond, ro, rd, z, rd_view=
         scratch = torch.empty(fam.fn("mlp_fwd_live_scratch_floats")(int(max_workgroups)), dtype=torch.float32, device=dev)
         waves = scratch.numel() * 4 // (LIVE_RING_ROWS * LIVE_ROW_BYTES)
         stats = torch.empty((waves, len(GATED_STAT_COLUMNS)), dtype=torch.int64, device=dev)
-        _gated_call("mlp_fwd_gated_stats", fam, packed, bound, cond, ro, rd, z, rd_view, max_workgroups, scratch, raw, stats.data_ptr(), waves,
+        _gated_call("mlp_fwd_gated_phases", fam, packed, bound, cond, ro, rd, z, rd_view, max_workgroups, scratch, raw, stats.data_ptr(), waves,
                     H.stream_ptr(dev))
     return raw, stats
 

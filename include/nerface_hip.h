@@ -631,7 +631,13 @@ int nf_paper_mlp_fwd_live(const float* packed, const float* cond, const float* r
  * nf_paper_mlp_fwd_live_stats: the same launch, same `raw`, through an instantiation of the kernel that records its schedule -- an
  * instrument for tests and profiles, not a render path.  stats: int64 [stats_rows][4] on the device, 8-byte aligned, stats_rows >=
  * 4 * (workgroups of the capped grid) = scratch floats / 4416; zeroed on the stream, then row (workgroup * 4 + wave) =
- * (units of 32 points the wave took, colour runs with the final flush, rows of the final flush, wall_clock64() at exit).          */
+ * (units of 32 points the wave took, colour runs with the final flush, rows of the final flush, wall_clock64() at exit).
+ * nf_paper_mlp_fwd_live_phases: the same with rows of 4 + 6: behind those four, six sums of shader clocks over the wave's passes --
+ * inputs and trunk up to the hook, hook and lone tile, ballot and append, a run's gathers up to its first MFMA, the run with its
+ * stores, the stores of the rows without a colour.                                                                                 */
+int nf_paper_mlp_fwd_live_phases(const float* packed, const float* cond, const float* ro, const float* rd, const float* rd_view,
+                                 const float* z, int64_t n_rays, int n_samples, float* raw, float* scratch, size_t scratch_floats,
+                                 int max_workgroups, int64_t* stats, size_t stats_rows, nf_stream_t stream);
 int nf_paper_mlp_fwd_live_stats(const float* packed, const float* cond, const float* ro, const float* rd, const float* rd_view,
                                 const float* z, int64_t n_rays, int n_samples, float* raw, float* scratch, size_t scratch_floats,
                                 int max_workgroups, int64_t* stats, size_t stats_rows, nf_stream_t stream);
@@ -645,7 +651,11 @@ int nf_paper_mlp_fwd_live_stats(const float* packed, const float* cond, const fl
  * bound: nf_paper_sigma_bound_floats() floats, 16-byte aligned, written by nf_paper_sigma_bound(packed, bound, stream) from the image
  * nf_paper_pack wrote: it is valid for that image, and `cond` must be a bias table of that image.  scratch, max_workgroups, the unit
  * counters: as nf_paper_mlp_fwd_live.  nf_paper_mlp_fwd_gated_stats: stats is int64 [stats_rows][5], nf_paper_mlp_fwd_live_stats' four
- * columns (a "colour run" is a gathered run) and the rows the wave proved dead.                                                     */
+ * columns (a "colour run" is a gathered run) and the rows the wave proved dead.  nf_paper_mlp_fwd_gated_phases: rows of 5 + 6, the six
+ * sums of clocks of nf_paper_mlp_fwd_live_phases behind them (the lone tile is the bound tile, a run a gathered run).               */
+int nf_paper_mlp_fwd_gated_phases(const float* packed, const float* bound, const float* cond, const float* ro, const float* rd,
+                                  const float* rd_view, const float* z, int64_t n_rays, int n_samples, float* raw, float* scratch,
+                                  size_t scratch_floats, int max_workgroups, int64_t* stats, size_t stats_rows, nf_stream_t stream);
 size_t nf_paper_sigma_bound_floats(void);
 int nf_paper_sigma_bound(const float* packed, float* bound, nf_stream_t stream);
 int nf_paper_mlp_fwd_gated(const float* packed, const float* bound, const float* cond, const float* ro, const float* rd,
