@@ -27,7 +27,9 @@ SOURCES = ["nf_lib.hip", "nf_rays.hip", "nf_choice.hip", "nf_render.hip", "nf_re
            # marching tetrahedra on a dense grid
            "nf_isosurface.hip",
            # which points of a dense grid lie near the surface: evaluate those, +-inf elsewhere
-           "nf_sparse_grid.hip"]
+           "nf_sparse_grid.hip",
+           # connected components of a mesh (union-find over the vertices), and the mesh of the components one rule keeps
+           "nf_mesh_components.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-fvisibility=default",
          "-Wno-unused-result"]
 

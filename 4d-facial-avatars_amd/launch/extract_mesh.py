@@ -3,13 +3,16 @@ launch/eval_sharded.py picks them), the raw density on a dense grid (nerf.densit
 (ops.isosurface), written as .ply / .obj / .off.  Single rank.
 
     python -m launch.extract_mesh --config cfg.yml --checkpoint ck --frame I --level L --resolution N [Ny Nz] --out mesh.ply \
-        [--bounds x0 y0 z0 x1 y1 z1] [--precision f32|f16x3|f16x2|bf16x3] [--coarse] [--brick B [--margin M] [--dilate D]]
+        [--bounds x0 y0 z0 x1 y1 z1] [--precision f32|f16x3|f16x2|bf16x3] [--coarse] [--brick B [--margin M] [--dilate D]] \
+        [--largest | --min-faces N]
 
 Without --bounds the box is the axis-aligned hull of the frame's camera frustum between the config's near and far planes (the
 four image-corner rays of nerf.get_ray_bundle).  --level is in raw-density units (before the renderer's ReLU) and has no default.
 With --brick B the network is evaluated only in the bricks of B cells near the surface (nerf.density_grid_sparse): first on the
 brick corners, then in every brick whose corners are not all on one side of the level by more than --margin, and in the bricks
 within --dilate bricks of those.  A feature thinner than a brick that passes between the corners is missed unless the margin is raised.
+--largest keeps the connected component with the most faces, --min-faces N every component with at least N faces (nerf.filter_mesh,
+on the device): a trained model's floaters are small components of their own.
 """
 from __future__ import annotations
 
@@ -54,6 +57,9 @@ def _main(argv=None):
     ap.add_argument("--brick", type=int, default=None, metavar="B", help="evaluate the density only in bricks of B cells near the surface (default: every point)")
     ap.add_argument("--margin", type=float, default=0.0, metavar="M", help="with --brick: corners within M of the level make their bricks seeds")
     ap.add_argument("--dilate", type=int, default=1, metavar="D", help="with --brick: also evaluate the bricks within D bricks of a seed (the normals need 1)")
+    rule = ap.add_mutually_exclusive_group()
+    rule.add_argument("--largest", action="store_true", help="keep only the connected component with the most faces")
+    rule.add_argument("--min-faces", type=int, default=None, metavar="N", help="keep only the connected components with at least N faces")
     args = ap.parse_args(argv)
     if len(args.resolution) not in (1, 3):
         ap.error("--resolution takes one number or three")
@@ -61,6 +67,8 @@ def _main(argv=None):
         ap.error("--out: the extension names the format (.ply, .obj or .off)")
     if args.brick is not None and (args.brick < 2 or not args.margin >= 0.0 or args.dilate < 1):
         ap.error("--brick takes at least 2 cells, --margin at least 0 and --dilate at least 1 (the mesh is written with normals)")
+    if args.min_faces is not None and args.min_faces < 1:
+        ap.error("--min-faces takes at least 1")
     if not torch.cuda.is_available():
         raise SystemExit("the MI355X `nerf` package needs a ROCm device")
     dev = torch.device("cuda", torch.cuda.current_device())
@@ -104,6 +112,10 @@ def _main(argv=None):
     ev[1].record()
     mesh = nerf.Mesh(*ops.isosurface(grid, args.level, lo, hi, normals=True))
     ev[2].record()
+    clean = None
+    if args.largest or args.min_faces is not None:
+        *kept, clean = ops.filter_mesh(*mesh, largest=args.largest, min_faces=args.min_faces)
+        mesh = nerf.Mesh(*kept)
     torch.cuda.synchronize()
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     nerf.write_mesh(args.out, mesh)
@@ -113,12 +125,16 @@ def _main(argv=None):
     print(f"frame {args.frame} ({stats['network']} network, {args.precision}): box lo {stats['lo']} hi {stats['hi']}, grid {stats['resolution']}, "
           f"level {args.level}: V = {stats['vertices']}, F = {stats['faces']}; density {stats['density_s']:.4f} s, extraction {stats['extract_s']:.4f} s "
           f"-> {args.out}")
+    if clean is not None:
+        stats["components"] = clean._asdict()
+        print(f"{'largest component' if args.largest else f'components of at least {args.min_faces} faces'}: {clean.components} components, "
+              f"{clean.kept_components} kept; vertices {clean.kept_vertices} of {clean.vertices}, faces {clean.kept_faces} of {clean.faces}")
     if sparse is not None:
         stats["sparse"] = sparse._asdict()
         print(f"bricks of {args.brick} cells (margin {args.margin}, dilate {args.dilate}): {sparse.seed_bricks} seed and {sparse.active_bricks} active of "
               f"{sparse.bricks} bricks; density evaluated on {sparse.evaluated_points} of {sparse.points} points "
               f"({100.0 * sparse.evaluated_points / sparse.points:.1f} %)")
-    if stats["faces"] == 0:
+    if (stats["faces"] if clean is None else clean.faces) == 0:
         seen = grid if sparse is None else grid[torch.isfinite(grid)]       # a sparse grid holds +-inf where nothing was evaluated
         lo_v, hi_v = seen.min().item(), seen.max().item()
         print(f"no surface at level {args.level}: the raw density on this grid spans [{lo_v:.4g}, {hi_v:.4g}]")

@@ -215,6 +215,11 @@ _PROTOTYPES["nf_sparse_grid_classify"] = (C.c_int, [_P, _I, _I, _I, _I, _F, _F, 
 _PROTOTYPES["nf_sparse_grid_mark"] = (C.c_int, [_I, _I, _I, _I, _P, _Z, _P, _P])
 _PROTOTYPES["nf_sparse_grid_emit"] = (C.c_int, [_P, _I, _I, _I, _I, _P, _P, _P, _Z, _P, _P, _L, _P])
 _PROTOTYPES["nf_sparse_grid_scatter"] = (C.c_int, [_P, _P, _L, _P, _I, _I, _I, _P])
+# connected components of an indexed mesh: label (C on the device), select (V', F', kept components on the device), emit
+_PROTOTYPES["nf_mesh_components_workspace_bytes"] = (_Z, [_L, _L])
+_PROTOTYPES["nf_mesh_components_label"] = (C.c_int, [_P, _L, _L, _P, _Z, _P, _P, _P, _P, _P, _P])
+_PROTOTYPES["nf_mesh_components_select"] = (C.c_int, [_P, _P, _P, _L, _L, _I, _L, _P, _Z, _P, _P])
+_PROTOTYPES["nf_mesh_components_emit"] = (C.c_int, [_P, _P, _P, _P, _P, _P, _L, _L, _P, _Z, _P, _L, _P, _L, _P, _P])
 for _prefix in ("nf_lcode", "nf_bshape", "nf_cbshape"):          # measurement hook (tools/time_blendshape.py)
     _PROTOTYPES[f"{_prefix}_mlp_bwd_stage_ms"] = (C.c_int, [_P, _P, _I, _P, _P, _P, _L, _I, _P, _Z, _P, _P, _P])
 # entry points that later ABI revisions add; absent symbols only fail when called

@@ -3,10 +3,13 @@
     density_grid(model, expr, latent_code, lo=, hi=, resolution=)          -> (nz, ny, nx) raw density on the device
     density_grid_sparse(..., lo=, hi=, resolution=, level=, brick=)        -> the same grid evaluated near the surface only, and its stats
     extract_mesh(model, expr, latent_code, lo=, hi=, resolution=, level=)  -> Mesh(vertices, faces, normals), device tensors
+    mesh_components(mesh)                                                  -> MeshComponents: labels and counts of the connected components
+    filter_mesh(mesh, largest= | min_faces=)                               -> the Mesh of the largest component, or of those of >= N faces
     write_mesh(path, mesh)                                                 -> .off / .obj / .ply (binary little-endian), host code
 
 The density comes from the density-only kernels (nerf.density), the surface from ops.isosurface (csrc/nf_isosurface.hip), the choice
-of the points near the surface from ops.sparse_grid (csrc/nf_sparse_grid.hip).
+of the points near the surface from ops.sparse_grid (csrc/nf_sparse_grid.hip), the components from ops.mesh_components and
+ops.filter_mesh (csrc/nf_mesh_components.hip).
 """
 from __future__ import annotations
 
@@ -72,14 +75,42 @@ def density_grid_sparse(model, expr, latent_code=None, *, lo, hi, resolution, le
                                dilate=dilate, chunk_points=chunk_points, device=expr.device)
 
 
+def _mesh_fields(mesh, what: str):
+    fields = tuple(mesh)
+    if len(fields) not in (2, 3):
+        raise ValueError(f"{what}: expected Mesh(vertices, faces, normals) or a (vertices, faces[, normals]) tuple")
+    return (fields + (None,))[:3]
+
+
+def mesh_components(mesh) -> ops.MeshComponents:
+    """Connected components of a Mesh (or a (vertices, faces[, normals]) tuple) on the device: ops.mesh_components of its faces over
+    its vertices -- MeshComponents(vertex_label, face_label, face_counts, vertex_counts), numbered by ascending smallest vertex id."""
+    vertices, faces, _ = _mesh_fields(mesh, "mesh_components")
+    if not torch.is_tensor(vertices) or vertices.dim() != 2 or vertices.shape[1] != 3:
+        raise ValueError("mesh_components: vertices must be a tensor of shape (V, 3)")
+    return ops.mesh_components(faces, vertices.shape[0])
+
+
+def filter_mesh(mesh, *, largest: bool = False, min_faces=None) -> Mesh:
+    """The Mesh of the components one rule keeps (ops.filter_mesh): largest=True, the component with the most faces, or min_faces=N,
+    every component with at least N faces -- a trained model's floaters are small components.  Order and bits of what is kept stay."""
+    vertices, faces, normals = _mesh_fields(mesh, "filter_mesh")
+    return Mesh(*ops.filter_mesh(vertices, faces, normals, largest=largest, min_faces=min_faces)[:3])
+
+
 def extract_mesh(model, expr, latent_code=None, *, lo, hi, resolution, level, normals: bool = True, chunk_points: int = 1 << 22, brick=None,
-                 margin: float = 0.0, dilate: int = 1) -> Mesh:
+                 margin: float = 0.0, dilate: int = 1, largest: bool = False, min_faces=None) -> Mesh:
     """The surface raw density == level of a fused model inside the box [lo, hi] for one expression (and latent code): density_grid,
     then ops.isosurface.  `level` is in raw-density units (before the ReLU of the volume renderer) and has no default: what counts
     as surface depends on the scene's scale and on how the model was trained.  With `brick` (cells per brick, e.g. 8) the grid is
     density_grid_sparse's: the network runs only in the bricks near the surface, and the mesh is the dense one wherever no brick
     hides a feature between its corners (`margin`, `dilate`: ops.sparse_grid).  The normals reach one point past a brick, so they
-    need dilate >= 1."""
+    need dilate >= 1.  With largest=True or min_faces=N the mesh is filter_mesh's: its largest component, or those of at least N
+    faces; with neither (the default) nothing more is launched."""
+    clean = largest or min_faces is not None
+    if clean and (bool(largest) == (min_faces is not None) or (min_faces is not None and (isinstance(min_faces, bool) or int(min_faces) != min_faces
+                                                                                          or int(min_faces) < 1))):
+        raise ValueError("extract_mesh: exactly one rule applies, largest=True or min_faces=N with N >= 1")
     if brick is None:
         grid = density_grid(model, expr, latent_code, lo=lo, hi=hi, resolution=resolution, chunk_points=chunk_points)
     else:
@@ -88,7 +119,8 @@ def extract_mesh(model, expr, latent_code=None, *, lo, hi, resolution, level, no
             raise ValueError("extract_mesh: normals=True needs dilate >= 1 (the central differences reach into the neighbouring brick)")
         grid, _ = density_grid_sparse(model, expr, latent_code, lo=lo, hi=hi, resolution=resolution, level=level, brick=brick, margin=margin,
                                       dilate=dilate, chunk_points=chunk_points)
-    return Mesh(*ops.isosurface(grid, float(level), lo, hi, normals=normals))
+    mesh = Mesh(*ops.isosurface(grid, float(level), lo, hi, normals=normals))
+    return filter_mesh(mesh, largest=largest, min_faces=min_faces) if clean else mesh
 
 
 def _host(mesh):

@@ -1275,6 +1275,122 @@ def isosurface(grid: torch.Tensor, level: float, lo, hi, normals: bool = False):
     return verts, faces, norm
 
 
+# ---------------------------------------------------------------------------------------- connected components of a mesh
+class MeshComponents(NamedTuple):
+    vertex_label: torch.Tensor                   # (V,) int32: the component of every vertex, 0 .. C-1 by ascending smallest vertex id
+    face_label: torch.Tensor                     # (F,) int32: the label of the face's first vertex, -1 for a face with an index outside [0, V)
+    face_counts: torch.Tensor                    # (C,) int32: valid faces per component
+    vertex_counts: torch.Tensor                  # (C,) int32: vertices per component
+
+
+class MeshFilterStats(NamedTuple):
+    components: int                              # components of the mesh (an unused vertex is one of its own)
+    kept_components: int
+    vertices: int
+    kept_vertices: int
+    faces: int
+    kept_faces: int
+
+
+def _check_faces(faces, n_vertices, what: str):
+    if not torch.is_tensor(faces) or faces.dtype != torch.int32 or faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError(f"{what}: faces must be an int32 tensor of shape (F, 3)")
+    n_vertices = int(n_vertices)
+    if not 0 <= n_vertices < 2 ** 31 or faces.shape[0] >= 2 ** 31:
+        raise ValueError(f"{what}: the numbers of vertices and faces lie in [0, 2^31), got {n_vertices} and {faces.shape[0]}")
+    return n_vertices, int(faces.shape[0])
+
+
+def _check_filter_args(vertices, faces, normals, largest, min_faces, what: str):
+    """Everything filter_mesh can refuse without a device; returns (V, F, largest, min_faces) with min_faces = 0 under `largest`."""
+    if not torch.is_tensor(vertices) or vertices.dtype != torch.float32 or vertices.dim() != 2 or vertices.shape[1] != 3:
+        raise ValueError(f"{what}: vertices must be a float32 tensor of shape (V, 3)")
+    n_vertices, n_faces = _check_faces(faces, vertices.shape[0], what)
+    if normals is not None and (not torch.is_tensor(normals) or normals.dtype != torch.float32 or normals.shape != vertices.shape):
+        raise ValueError(f"{what}: normals must be None or a float32 tensor of the vertices' shape {tuple(vertices.shape)}")
+    largest = bool(largest)
+    if largest == (min_faces is not None):
+        raise ValueError(f"{what}: exactly one rule applies, largest=True or min_faces=N")
+    if min_faces is not None:
+        if isinstance(min_faces, bool) or int(min_faces) != min_faces or not 1 <= int(min_faces) < 2 ** 63:
+            raise ValueError(f"{what}: min_faces is a whole number of at least 1, got {min_faces!r}")
+        min_faces = int(min_faces)
+    return n_vertices, n_faces, largest, min_faces or 0
+
+
+def _mesh_components_workspace(lib, n_vertices, n_faces, dev, what):
+    ws_bytes = int(lib.nf_mesh_components_workspace_bytes(n_vertices, n_faces))
+    if ws_bytes == 0:
+        raise ValueError(f"{what}: {n_vertices} vertices and {n_faces} faces are past the plan of csrc/nf_mesh_components.hip (both below 2^31)")
+    return torch.empty(ws_bytes, dtype=torch.uint8, device=dev), ws_bytes
+
+
+def _require_same_device(what, first, *others):
+    if not first.is_cuda:
+        raise RuntimeError("nerf (MI355X build): tensors must live on a ROCm device (`device='cuda'`); there is no CPU path in this package")
+    for t in others:
+        if t is not None and t.device != first.device:
+            raise RuntimeError(f"{what}: tensors are on different devices")
+    return first.device
+
+
+def _label_mesh(lib, faces, n_vertices, n_faces, ws, ws_bytes, counts, dev):
+    """The launches of nf_mesh_components_label into fresh buffers (the counts hold V entries, of which C are written)."""
+    i32 = lambda n: torch.empty(n, dtype=torch.int32, device=dev)
+    vertex_label, face_label, face_counts, vertex_counts = i32(n_vertices), i32(n_faces), i32(n_vertices), i32(n_vertices)
+    H.check(lib.nf_mesh_components_label(H.ptr(faces), n_vertices, n_faces, H.ptr(ws), ws_bytes, H.ptr(vertex_label), H.ptr(face_label),
+                                         H.ptr(face_counts), H.ptr(vertex_counts), H.ptr(counts), H.stream_ptr(dev)), "nf_mesh_components_label")
+    return vertex_label, face_label, face_counts, vertex_counts
+
+
+def mesh_components(faces: torch.Tensor, n_vertices: int) -> MeshComponents:
+    """Connected components of the mesh `faces` (F, 3) int32 over n_vertices vertices, on a ROCm device (DESIGN.md "Mesh components"):
+    two vertices are connected iff a chain of faces links them, a shared vertex being enough; a face with an index outside
+    [0, n_vertices) takes no part and is labelled -1; a vertex no face uses is a component of its own.  Components are numbered by
+    ascending smallest vertex id.  Union-find on the device (csrc/nf_mesh_components.hip), the same bits from run to run.  Exactly
+    one host read: the number of components, which sizes the counts."""
+    n_vertices, n_faces = _check_faces(faces, n_vertices, "mesh_components")
+    dev = _require_same_device("mesh_components", faces)
+    faces = faces.detach().contiguous()
+    lib = H.lib()
+    ws, ws_bytes = _mesh_components_workspace(lib, n_vertices, n_faces, dev, "mesh_components")
+    counts = torch.empty(4, dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        vertex_label, face_label, face_counts, vertex_counts = _label_mesh(lib, faces, n_vertices, n_faces, ws, ws_bytes, counts, dev)
+        n_components = int(counts[0].item())                            # the one host read
+    return MeshComponents(vertex_label, face_label, face_counts[:n_components].clone(), vertex_counts[:n_components].clone())
+
+
+def filter_mesh(vertices: torch.Tensor, faces: torch.Tensor, normals: Optional[torch.Tensor] = None, *, largest: bool = False, min_faces=None):
+    """The mesh of the components one rule keeps: largest=True, the component with the most faces (ties: the one with the smallest
+    vertex id; nothing if no component has a face), or min_faces=N >= 1, every component with at least N faces.  Kept vertices and
+    the faces of kept components stay in their order, the indices are renumbered, vertex and normal rows are copied bit for bit; a
+    face with an index outside [0, V) is never kept.  Returns (vertices, faces, normals or None, MeshFilterStats); an empty result
+    is made of (0, 3) tensors.  Labelling, selection and compaction run on the device with exactly one host read (the counts that
+    size the outputs)."""
+    n_vertices, n_faces, largest, min_faces = _check_filter_args(vertices, faces, normals, largest, min_faces, "filter_mesh")
+    dev = _require_same_device("filter_mesh", vertices, faces, normals)
+    vertices, faces = vertices.detach().contiguous(), faces.detach().contiguous()
+    normals = None if normals is None else normals.detach().contiguous()
+    lib = H.lib()
+    ws, ws_bytes = _mesh_components_workspace(lib, n_vertices, n_faces, dev, "filter_mesh")
+    counts = torch.empty(4, dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        stream = H.stream_ptr(dev)
+        vertex_label, face_label, face_counts, _ = _label_mesh(lib, faces, n_vertices, n_faces, ws, ws_bytes, counts, dev)
+        H.check(lib.nf_mesh_components_select(H.ptr(vertex_label), H.ptr(face_label), H.ptr(face_counts), n_vertices, n_faces, int(largest), min_faces,
+                                              H.ptr(ws), ws_bytes, H.ptr(counts), stream), "nf_mesh_components_select")
+        n_components, kept_v, kept_f, kept_c = counts.tolist()          # the one host read
+        out_v = torch.empty((kept_v, 3), dtype=torch.float32, device=dev)
+        out_f = torch.empty((kept_f, 3), dtype=torch.int32, device=dev)
+        out_n = None if normals is None else torch.empty((kept_v, 3), dtype=torch.float32, device=dev)
+        if kept_v:
+            H.check(lib.nf_mesh_components_emit(H.ptr(vertices), H.ptr(faces), H.ptr(normals), H.ptr(vertex_label), H.ptr(face_label),
+                                                H.ptr(face_counts), n_vertices, n_faces, H.ptr(ws), ws_bytes, H.ptr(out_v), kept_v, H.ptr(out_f),
+                                                kept_f, H.ptr(out_n), stream), "nf_mesh_components_emit")
+    return out_v, out_f, out_n, MeshFilterStats(n_components, kept_c, n_vertices, kept_v, n_faces, kept_f)
+
+
 # ---------------------------------------------------------------------------------------- sparse evaluation of a dense grid
 class SparseGridStats(NamedTuple):
     bricks: int                                  # bricks of the grid

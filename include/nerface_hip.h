@@ -716,6 +716,36 @@ int nf_sparse_grid_emit(float* grid, int nx, int ny, int nz, int brick, const fl
 int nf_sparse_grid_scatter(const float* values, const int* index, int64_t count, float* grid, int nx, int ny, int nz,
                            nf_stream_t stream);
 
+/* ---- connected components of an indexed mesh, and the mesh of the kept ones (ABI 5 still: these only add) ------------------------
+ * faces: int32 [F][3] over V vertices, 0 <= V, F < 2^31 (DESIGN.md "Mesh components" is the specification).  A face is valid iff
+ * its three indices lie in [0, V); vertices are connected through valid faces (a shared vertex is enough); components are numbered
+ * 0 .. C-1 by ascending smallest vertex id.  workspace: nf_mesh_components_workspace_bytes(V, F) bytes, 8-byte aligned, any content,
+ * the same buffer through label, select and emit; 0 = a size that is not served (negative, or 2^31 and above).
+ *   nf_mesh_components_label   vertex_label[V]; face_label[F] = the label of the face's first vertex, -1 for an invalid face;
+ *                              face_counts / vertex_counts: buffers of V entries, of which the first C are written (valid faces and
+ *                              vertices per component); counts_dev[0] = C (int64, on the device).
+ *   nf_mesh_components_select  with those arrays and the workspace as label left it: the component with the most faces, ties to the
+ *                              lower label, none if no component has a face (largest != 0, min_faces == 0), or every component with
+ *                              at least min_faces >= 1 faces (largest == 0); counts_dev[1] = kept vertices, [2] = kept faces,
+ *                              [3] = kept components ([0] is left alone).
+ *   nf_mesh_components_emit    with the workspace as select left it: the kept vertices and the valid faces of kept components in
+ *                              their original order, indices renumbered; vertex (and, unless both are NULL, normal) rows copied bit
+ *                              for bit.  cap_vertices / cap_faces are the CAPACITIES of the outputs in rows: no row at or past them
+ *                              is written.
+ * NF_EINVAL before any device call: NULL pointers where the size is not 0, an unserved size, workspace_bytes too small, both rules
+ * or neither, a negative min_faces or capacity, normals without out_normals or the reverse.  Two calls give the same bits.      */
+size_t nf_mesh_components_workspace_bytes(int64_t n_vertices, int64_t n_faces);
+int nf_mesh_components_label(const int* faces, int64_t n_vertices, int64_t n_faces, void* workspace, size_t workspace_bytes,
+                             int* vertex_label, int* face_label, int* face_counts, int* vertex_counts, int64_t* counts_dev,
+                             nf_stream_t stream);
+int nf_mesh_components_select(const int* vertex_label, const int* face_label, const int* face_counts, int64_t n_vertices,
+                              int64_t n_faces, int largest, int64_t min_faces, void* workspace, size_t workspace_bytes,
+                              int64_t* counts_dev, nf_stream_t stream);
+int nf_mesh_components_emit(const float* vertices, const int* faces, const float* normals, const int* vertex_label,
+                            const int* face_label, const int* face_counts, int64_t n_vertices, int64_t n_faces, void* workspace,
+                            size_t workspace_bytes, float* out_vertices, int64_t cap_vertices, int* out_faces, int64_t cap_faces,
+                            float* out_normals, nf_stream_t stream);
+
 /* ---- host-only self-tests (no device needed): consistency of the weight-gradient job tables -- every slab entry written
  * exactly once per slice, tile ids inside their bundle.  0 = consistent, negative = which check failed.                 */
 int nf_selftest_dw_tables_f32(void);
