@@ -265,6 +265,7 @@ static inline void nf_tiny_bwd_plan(int64_t n_points, int64_t* pts_per_slice, in
 }
 
 extern "C" size_t nf_tiny_bwd_workspace_floats(int64_t n_points) {
+    if (n_points <= 0) return 0;
     int64_t pps; int ns;
     nf_tiny_bwd_plan(n_points, &pps, &ns);
     return (size_t)nft::DZ_PER_POINT * (size_t)n_points + (size_t)(ns + 1) * nft::SLAB;
