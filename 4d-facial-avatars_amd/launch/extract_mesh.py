@@ -4,7 +4,7 @@ launch/eval_sharded.py picks them), the raw density on a dense grid (nerf.densit
 
     python -m launch.extract_mesh --config cfg.yml --checkpoint ck --frame I --level L --resolution N [Ny Nz] --out mesh.ply \
         [--bounds x0 y0 z0 x1 y1 z1] [--precision f32|f16x3|f16x2|bf16x3] [--coarse] [--brick B [--margin M] [--dilate D]] \
-        [--largest | --min-faces N]
+        [--largest | --min-faces N] [--smooth N [--smooth-lambda L] [--smooth-mu M]]
 
 Without --bounds the box is the axis-aligned hull of the frame's camera frustum between the config's near and far planes (the
 four image-corner rays of nerf.get_ray_bundle).  --level is in raw-density units (before the renderer's ReLU) and has no default.
@@ -12,7 +12,9 @@ With --brick B the network is evaluated only in the bricks of B cells near the s
 brick corners, then in every brick whose corners are not all on one side of the level by more than --margin, and in the bricks
 within --dilate bricks of those.  A feature thinner than a brick that passes between the corners is missed unless the margin is raised.
 --largest keeps the connected component with the most faces, --min-faces N every component with at least N faces (nerf.filter_mesh,
-on the device): a trained model's floaters are small components of their own.
+on the device): a trained model's floaters are small components of their own.  --smooth N runs N iterations of Taubin's lambda | mu
+smoothing on what is left (nerf.smooth_mesh, on the device; the border a box cuts into the surface stays where it is) and writes
+the normals of the smoothed faces in place of the density gradient's.
 """
 from __future__ import annotations
 
@@ -60,6 +62,9 @@ def _main(argv=None):
     rule = ap.add_mutually_exclusive_group()
     rule.add_argument("--largest", action="store_true", help="keep only the connected component with the most faces")
     rule.add_argument("--min-faces", type=int, default=None, metavar="N", help="keep only the connected components with at least N faces")
+    ap.add_argument("--smooth", type=int, default=0, metavar="N", help="iterations of Taubin smoothing after the component filter (default: none)")
+    ap.add_argument("--smooth-lambda", type=float, default=0.5, metavar="L", help="with --smooth: the shrinking factor, 0 < L <= 1")
+    ap.add_argument("--smooth-mu", type=float, default=-0.53, metavar="M", help="with --smooth: the inflating factor, -1 <= M <= 0 (0: plain Laplacian smoothing)")
     args = ap.parse_args(argv)
     if len(args.resolution) not in (1, 3):
         ap.error("--resolution takes one number or three")
@@ -69,6 +74,8 @@ def _main(argv=None):
         ap.error("--brick takes at least 2 cells, --margin at least 0 and --dilate at least 1 (the mesh is written with normals)")
     if args.min_faces is not None and args.min_faces < 1:
         ap.error("--min-faces takes at least 1")
+    if args.smooth < 0 or not 0.0 < args.smooth_lambda <= 1.0 or not -1.0 <= args.smooth_mu <= 0.0:
+        ap.error("--smooth takes at least 0 iterations, --smooth-lambda a factor in (0, 1] and --smooth-mu one in [-1, 0]")
     if not torch.cuda.is_available():
         raise SystemExit("the MI355X `nerf` package needs a ROCm device")
     dev = torch.device("cuda", torch.cuda.current_device())
@@ -116,6 +123,10 @@ def _main(argv=None):
     if args.largest or args.min_faces is not None:
         *kept, clean = ops.filter_mesh(*mesh, largest=args.largest, min_faces=args.min_faces)
         mesh = nerf.Mesh(*kept)
+    smooth = None
+    if args.smooth:
+        *smoothed, smooth = ops.smooth_mesh(*mesh, iterations=args.smooth, lam=args.smooth_lambda, mu=args.smooth_mu)
+        mesh = nerf.Mesh(*smoothed)
     torch.cuda.synchronize()
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     nerf.write_mesh(args.out, mesh)
@@ -129,6 +140,10 @@ def _main(argv=None):
         stats["components"] = clean._asdict()
         print(f"{'largest component' if args.largest else f'components of at least {args.min_faces} faces'}: {clean.components} components, "
               f"{clean.kept_components} kept; vertices {clean.kept_vertices} of {clean.vertices}, faces {clean.kept_faces} of {clean.faces}")
+    if smooth is not None:
+        stats["smooth"] = smooth._asdict()
+        print(f"smoothed: {args.smooth} iterations (lambda {args.smooth_lambda}, mu {args.smooth_mu}) in {smooth.passes} passes over {smooth.edges // 2} edges; "
+              f"{smooth.pinned_vertices} boundary vertices of {stats['vertices']} stay where they are")
     if sparse is not None:
         stats["sparse"] = sparse._asdict()
         print(f"bricks of {args.brick} cells (margin {args.margin}, dilate {args.dilate}): {sparse.seed_bricks} seed and {sparse.active_bricks} active of "

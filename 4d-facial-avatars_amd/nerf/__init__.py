@@ -25,5 +25,6 @@ from .ops import image_metrics, quantize_image  # MI355X extension: L1 / PSNR / 
 from .models import density  # MI355X extension: raw sigma of a fused model at arbitrary points, from the density-only kernels
 from .mesh import density_grid_sparse  # MI355X extension: that grid evaluated only in the bricks near one level's surface (ops.sparse_grid)
 from .mesh import Mesh, density_grid, extract_mesh, write_mesh  # MI355X extension: a model's density on a grid and the triangle mesh of one level (ops.isosurface)
+from .mesh import smooth_mesh, vertex_normals  # MI355X extension: Taubin smoothing of a mesh and the unit normals of its faces (ops.smooth_mesh, ops.vertex_normals)
 from .mesh import filter_mesh, mesh_components  # MI355X extension: a mesh's connected components; its largest, or those of at least N faces (ops.filter_mesh)
 from .train_graph import GraphedTrainer  # MI355X extension: the training iteration captured once in a HIP graph and replayed (single rank)

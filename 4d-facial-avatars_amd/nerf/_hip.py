@@ -220,6 +220,12 @@ _PROTOTYPES["nf_mesh_components_workspace_bytes"] = (_Z, [_L, _L])
 _PROTOTYPES["nf_mesh_components_label"] = (C.c_int, [_P, _L, _L, _P, _Z, _P, _P, _P, _P, _P, _P])
 _PROTOTYPES["nf_mesh_components_select"] = (C.c_int, [_P, _P, _P, _L, _L, _I, _L, _P, _Z, _P, _P])
 _PROTOTYPES["nf_mesh_components_emit"] = (C.c_int, [_P, _P, _P, _P, _P, _P, _L, _L, _P, _Z, _P, _L, _P, _L, _P, _P])
+# Taubin smoothing of an indexed mesh: the CSR table of the neighbours (E and the boundary vertices on the device), all passes in one
+# call, and the vertex normals of the faces
+_PROTOTYPES["nf_mesh_smooth_workspace_bytes"] = (_Z, [_L, _L])
+_PROTOTYPES["nf_mesh_smooth_adjacency"] = (C.c_int, [_P, _L, _L, _P, _Z, _P, _P, _P, _P, _P, _P])
+_PROTOTYPES["nf_mesh_smooth_run"] = (C.c_int, [_P, _L, _P, _P, _P, _I, _F, _F, _P, _P, _P])
+_PROTOTYPES["nf_mesh_smooth_normals"] = (C.c_int, [_P, _P, _L, _L, _P, _Z, _P, _P])
 for _prefix in ("nf_lcode", "nf_bshape", "nf_cbshape"):          # measurement hook (tools/time_blendshape.py)
     _PROTOTYPES[f"{_prefix}_mlp_bwd_stage_ms"] = (C.c_int, [_P, _P, _I, _P, _P, _P, _L, _I, _P, _Z, _P, _P, _P])
 # entry points that later ABI revisions add; absent symbols only fail when called

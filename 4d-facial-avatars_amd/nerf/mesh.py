@@ -5,11 +5,14 @@
     extract_mesh(model, expr, latent_code, lo=, hi=, resolution=, level=)  -> Mesh(vertices, faces, normals), device tensors
     mesh_components(mesh)                                                  -> MeshComponents: labels and counts of the connected components
     filter_mesh(mesh, largest= | min_faces=)                               -> the Mesh of the largest component, or of those of >= N faces
+    smooth_mesh(mesh, iterations=, lam=, mu=, fix_boundary=)               -> the Mesh after Taubin smoothing, its normals recomputed
+    vertex_normals(mesh)                                                   -> (V, 3) unit normals from the faces
     write_mesh(path, mesh)                                                 -> .off / .obj / .ply (binary little-endian), host code
 
 The density comes from the density-only kernels (nerf.density), the surface from ops.isosurface (csrc/nf_isosurface.hip), the choice
 of the points near the surface from ops.sparse_grid (csrc/nf_sparse_grid.hip), the components from ops.mesh_components and
-ops.filter_mesh (csrc/nf_mesh_components.hip).
+ops.filter_mesh (csrc/nf_mesh_components.hip), smoothing and face normals from ops.smooth_mesh and ops.vertex_normals
+(csrc/nf_mesh_smooth.hip).
 """
 from __future__ import annotations
 
@@ -98,15 +101,40 @@ def filter_mesh(mesh, *, largest: bool = False, min_faces=None) -> Mesh:
     return Mesh(*ops.filter_mesh(vertices, faces, normals, largest=largest, min_faces=min_faces)[:3])
 
 
+def smooth_mesh(mesh, *, iterations: int = 10, lam: float = 0.5, mu: float = -0.53, fix_boundary: bool = True) -> Mesh:
+    """The Mesh (or (vertices, faces[, normals]) tuple) after `iterations` of Taubin's lambda | mu smoothing (ops.smooth_mesh): the
+    marching-tetrahedra staircase and the wobble of a learned density go, the volume stays (mu < -lam; mu = 0 is plain Laplacian
+    smoothing, which shrinks), the vertices on an open border stay where they are under fix_boundary.  Faces as given; normals, if
+    the mesh has them, become vertex_normals of the smoothed positions.  iterations = 0 returns the mesh's own tensors."""
+    vertices, faces, normals = _mesh_fields(mesh, "smooth_mesh")
+    return Mesh(*ops.smooth_mesh(vertices, faces, normals, iterations=iterations, lam=lam, mu=mu, fix_boundary=fix_boundary)[:3])
+
+
+def vertex_normals(mesh) -> torch.Tensor:
+    """(V, 3) unit normals of a Mesh (or tuple) from its faces (ops.vertex_normals): area-weighted, towards lower density for the
+    faces of extract_mesh, zero for a vertex no face uses."""
+    vertices, faces, _ = _mesh_fields(mesh, "vertex_normals")
+    return ops.vertex_normals(vertices, faces)
+
+
 def extract_mesh(model, expr, latent_code=None, *, lo, hi, resolution, level, normals: bool = True, chunk_points: int = 1 << 22, brick=None,
-                 margin: float = 0.0, dilate: int = 1, largest: bool = False, min_faces=None) -> Mesh:
+                 margin: float = 0.0, dilate: int = 1, largest: bool = False, min_faces=None, smooth: int = 0, smooth_lam: float = 0.5,
+                 smooth_mu: float = -0.53) -> Mesh:
     """The surface raw density == level of a fused model inside the box [lo, hi] for one expression (and latent code): density_grid,
     then ops.isosurface.  `level` is in raw-density units (before the ReLU of the volume renderer) and has no default: what counts
     as surface depends on the scene's scale and on how the model was trained.  With `brick` (cells per brick, e.g. 8) the grid is
     density_grid_sparse's: the network runs only in the bricks near the surface, and the mesh is the dense one wherever no brick
     hides a feature between its corners (`margin`, `dilate`: ops.sparse_grid).  The normals reach one point past a brick, so they
     need dilate >= 1.  With largest=True or min_faces=N the mesh is filter_mesh's: its largest component, or those of at least N
-    faces; with neither (the default) nothing more is launched."""
+    faces; with neither (the default) nothing more is launched.  With smooth=N the result is smooth_mesh's after N iterations with
+    smooth_lam and smooth_mu, run after the component filter, so that floaters are not smoothed; at the default 0 nothing more is
+    launched."""
+    try:
+        whole = not isinstance(smooth, bool) and int(smooth) == smooth and int(smooth) >= 0
+    except (TypeError, ValueError, OverflowError):
+        whole = False
+    if not whole:
+        raise ValueError(f"extract_mesh: smooth is a whole number of iterations, at least 0, got {smooth!r}")
     clean = largest or min_faces is not None
     if clean and (bool(largest) == (min_faces is not None) or (min_faces is not None and (isinstance(min_faces, bool) or int(min_faces) != min_faces
                                                                                           or int(min_faces) < 1))):
@@ -120,7 +148,9 @@ def extract_mesh(model, expr, latent_code=None, *, lo, hi, resolution, level, no
         grid, _ = density_grid_sparse(model, expr, latent_code, lo=lo, hi=hi, resolution=resolution, level=level, brick=brick, margin=margin,
                                       dilate=dilate, chunk_points=chunk_points)
     mesh = Mesh(*ops.isosurface(grid, float(level), lo, hi, normals=normals))
-    return filter_mesh(mesh, largest=largest, min_faces=min_faces) if clean else mesh
+    if clean:
+        mesh = filter_mesh(mesh, largest=largest, min_faces=min_faces)
+    return smooth_mesh(mesh, iterations=int(smooth), lam=smooth_lam, mu=smooth_mu) if int(smooth) else mesh
 
 
 def _host(mesh):

@@ -1391,6 +1391,147 @@ def filter_mesh(vertices: torch.Tensor, faces: torch.Tensor, normals: Optional[t
     return out_v, out_f, out_n, MeshFilterStats(n_components, kept_c, n_vertices, kept_v, n_faces, kept_f)
 
 
+# ---------------------------------------------------------------------------------------- Taubin smoothing of a mesh
+MESH_SMOOTH_SHORT_ROW = 32                       # nfs::SHORT_ROW of csrc/nf_mesh_smooth.hip: a row of the vertex -> neighbours (or vertex -> faces)
+                                                 # table of at most this many entries, repeats included, is sorted by one thread, a longer one by a wave
+
+
+class MeshAdjacency(NamedTuple):
+    row_start: torch.Tensor                      # (V + 1,) int32: row v of the two arrays below is [row_start[v], row_start[v + 1])
+    neighbours: torch.Tensor                     # (E,) int32: the distinct w != v that a side of a valid face joins to v, ascending
+    multiplicity: torch.Tensor                   # (E,) int32: the number of sides joining v and w (2 inside a closed surface)
+    boundary: torch.Tensor                       # (V,) uint8: 1 iff v is an end of an edge of multiplicity 1
+
+
+class MeshSmoothStats(NamedTuple):
+    edges: int                                   # E: directed pairs, twice the number of edges
+    boundary_vertices: int
+    pinned_vertices: int                         # the boundary vertices under fix_boundary, else 0
+    passes: int                                  # launches of the pass kernel: iterations, twice that with mu != 0
+
+
+def _check_smooth_sizes(n_vertices, n_faces, what: str):
+    if not 0 <= n_vertices < 2 ** 31 or not 6 * n_faces < 2 ** 31:
+        raise ValueError(f"{what}: V and 6 F lie in [0, 2^31) (ids and table positions are int32), got V = {n_vertices} and F = {n_faces}")
+
+
+def _check_smooth_mesh(vertices, faces, what: str):
+    if not torch.is_tensor(vertices) or vertices.dtype != torch.float32 or vertices.dim() != 2 or vertices.shape[1] != 3:
+        raise ValueError(f"{what}: vertices must be a float32 tensor of shape (V, 3)")
+    n_vertices, n_faces = _check_faces(faces, vertices.shape[0], what)
+    _check_smooth_sizes(n_vertices, n_faces, what)
+    return n_vertices, n_faces
+
+
+def _check_smooth_args(vertices, faces, normals, iterations, lam, mu, what: str):
+    """Everything smooth_mesh can refuse without a device; returns (V, F, iterations, lam, mu), the factors rounded to float32."""
+    n_vertices, n_faces = _check_smooth_mesh(vertices, faces, what)
+    if normals is not None and (not torch.is_tensor(normals) or normals.dtype != torch.float32 or normals.shape != vertices.shape):
+        raise ValueError(f"{what}: normals must be None or a float32 tensor of the vertices' shape {tuple(vertices.shape)}")
+    try:
+        whole = not isinstance(iterations, bool) and int(iterations) == iterations and 0 <= int(iterations) < 2 ** 30
+    except (TypeError, ValueError, OverflowError):
+        whole = False
+    if not whole:
+        raise ValueError(f"{what}: iterations is a whole number of at least 0 (and below 2^30), got {iterations!r}")
+    try:
+        lam32, mu32 = float(np.float32(lam)), float(np.float32(mu))
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: lam and mu are numbers, got {lam!r} and {mu!r}")
+    if not (0.0 < lam32 <= 1.0) or not (-1.0 <= mu32 <= 0.0):                 # not finite fails both
+        raise ValueError(f"{what}: 0 < lam <= 1 and -1 <= mu <= 0 (in float32), got lam = {lam!r} and mu = {mu!r}")
+    return n_vertices, n_faces, int(iterations), lam32, mu32
+
+
+def _mesh_smooth_workspace(lib, n_vertices, n_faces, dev, what):
+    ws_bytes = int(lib.nf_mesh_smooth_workspace_bytes(n_vertices, n_faces))
+    if ws_bytes == 0:
+        raise ValueError(f"{what}: {n_vertices} vertices and {n_faces} faces are past the plan of csrc/nf_mesh_smooth.hip (V and 6 F below 2^31)")
+    return torch.empty(ws_bytes, dtype=torch.uint8, device=dev), ws_bytes
+
+
+def _adjacency(lib, faces, n_vertices, n_faces, dev):
+    """The launches of nf_mesh_smooth_adjacency into fresh buffers: row_start, the two arrays of 6 F entries (the first E written),
+    boundary and the device counts {E, boundary vertices}."""
+    ws, ws_bytes = _mesh_smooth_workspace(lib, n_vertices, n_faces, dev, "mesh_adjacency")
+    row_start = torch.empty(n_vertices + 1, dtype=torch.int32, device=dev)
+    neighbours = torch.empty(max(6 * n_faces, 1), dtype=torch.int32, device=dev)       # never NULL: the pass takes the table of a mesh without faces
+    multiplicity = torch.empty(max(6 * n_faces, 1), dtype=torch.int32, device=dev)
+    boundary = torch.empty(n_vertices, dtype=torch.uint8, device=dev)
+    counts = torch.empty(2, dtype=torch.int64, device=dev)
+    H.check(lib.nf_mesh_smooth_adjacency(H.ptr(faces), n_vertices, n_faces, H.ptr(ws), ws_bytes, H.ptr(row_start), H.ptr(neighbours), H.ptr(multiplicity),
+                                         H.ptr(boundary), H.ptr(counts), H.stream_ptr(dev)), "nf_mesh_smooth_adjacency")
+    return row_start, neighbours, multiplicity, boundary, counts
+
+
+def mesh_adjacency(faces: torch.Tensor, n_vertices: int) -> MeshAdjacency:
+    """The neighbours of every vertex of the mesh `faces` (F, 3) int32 over n_vertices vertices, on a ROCm device, as CSR (DESIGN.md
+    "Mesh smoothing"): a face with an index outside [0, n_vertices) takes no part; a valid face (a, b, c) has the sides ab, bc, ca,
+    of which those with equal ends are dropped; row v holds the distinct w != v joined to v by a side, ascending, and how many sides
+    join them (a face listed twice counts twice); a vertex is on the boundary iff it ends an edge of multiplicity 1.  Built by
+    csrc/nf_mesh_smooth.hip with integer arithmetic only, the same bits from run to run.  Exactly one host read: E, which sizes
+    the two arrays."""
+    n_vertices, n_faces = _check_faces(faces, n_vertices, "mesh_adjacency")
+    _check_smooth_sizes(n_vertices, n_faces, "mesh_adjacency")
+    dev = _require_same_device("mesh_adjacency", faces)
+    faces = faces.detach().contiguous()
+    lib = H.lib()
+    with torch.cuda.device(dev):
+        row_start, neighbours, multiplicity, boundary, counts = _adjacency(lib, faces, n_vertices, n_faces, dev)
+        n_edges = int(counts[0].item())                                 # the one host read
+    return MeshAdjacency(row_start, neighbours[:n_edges].clone(), multiplicity[:n_edges].clone(), boundary)
+
+
+def _vertex_normals(lib, vertices, faces, n_vertices, n_faces, dev):
+    ws, ws_bytes = _mesh_smooth_workspace(lib, n_vertices, n_faces, dev, "vertex_normals")
+    out = torch.empty((n_vertices, 3), dtype=torch.float32, device=dev)
+    H.check(lib.nf_mesh_smooth_normals(H.ptr(vertices), H.ptr(faces), n_vertices, n_faces, H.ptr(ws), ws_bytes, H.ptr(out), H.stream_ptr(dev)),
+            "nf_mesh_smooth_normals")
+    return out
+
+
+def vertex_normals(vertices: torch.Tensor, faces: torch.Tensor) -> torch.Tensor:
+    """(V, 3) float32 unit normals of the mesh's vertices from its faces: per valid face (p[b] - p[a]) x (p[c] - p[a]), per vertex the
+    sum of those vectors over the faces that hold it (each face once, in ascending face order -- the same bits from run to run),
+    divided by its length; the zero vector where the sum is zero or not finite (ops.isosurface's convention), as for a vertex no
+    face uses.  The faces of ops.isosurface are counter-clockwise seen from lower density, so these point the way its normals do.
+    No host read."""
+    n_vertices, n_faces = _check_smooth_mesh(vertices, faces, "vertex_normals")
+    dev = _require_same_device("vertex_normals", vertices, faces)
+    vertices, faces = vertices.detach().contiguous(), faces.detach().contiguous()
+    lib = H.lib()
+    with torch.cuda.device(dev):
+        return _vertex_normals(lib, vertices, faces, n_vertices, n_faces, dev)
+
+
+def smooth_mesh(vertices: torch.Tensor, faces: torch.Tensor, normals: Optional[torch.Tensor] = None, *, iterations: int = 10, lam: float = 0.5,
+                mu: float = -0.53, fix_boundary: bool = True):
+    """Taubin's lambda | mu smoothing of a mesh on a ROCm device (DESIGN.md "Mesh smoothing").  Every iteration is a pass with `lam`
+    and then, unless mu == 0, a pass with `mu`; a pass moves every vertex by its factor times (the mean of its neighbours - itself),
+    all vertices at once from the positions before the pass.  0 < lam <= 1 shrinks, -1 <= mu <= 0 inflates again: mu < -lam is what
+    keeps the volume (the defaults are Taubin's 0.5 and -0.53), and mu = 0 is plain Laplacian smoothing, which shrinks.  With
+    fix_boundary (the default) the vertices of the mesh's open border -- the ends of edges that only one face side uses -- stay
+    where they are, so a surface cut by the extraction box keeps its cut.  Vertices without neighbours stay too.  Returns
+    (vertices, faces, normals or None, MeshSmoothStats): faces as given; normals, if given, are replaced by vertex_normals of the
+    smoothed positions (the given ones belong to positions that no longer exist).  iterations = 0 returns the inputs as they are
+    and launches nothing (the stats then hold zeros).  Sums run in ascending neighbour order without float atomics: the same bits
+    from run to run.  Exactly one host read (the counts of the stats)."""
+    n_vertices, n_faces, iterations, lam, mu = _check_smooth_args(vertices, faces, normals, iterations, lam, mu, "smooth_mesh")
+    dev = _require_same_device("smooth_mesh", vertices, faces, normals)
+    if iterations == 0:
+        return vertices, faces, normals, MeshSmoothStats(0, 0, 0, 0)
+    vertices_in, faces_in = vertices.detach().contiguous(), faces.detach().contiguous()
+    lib = H.lib()
+    with torch.cuda.device(dev):
+        row_start, neighbours, _, boundary, counts = _adjacency(lib, faces_in, n_vertices, n_faces, dev)
+        out, tmp = torch.empty_like(vertices_in), torch.empty_like(vertices_in)
+        H.check(lib.nf_mesh_smooth_run(H.ptr(vertices_in), n_vertices, H.ptr(row_start), H.ptr(neighbours), H.ptr(boundary) if fix_boundary else 0, iterations,
+                                       lam, mu, H.ptr(tmp), H.ptr(out), H.stream_ptr(dev)), "nf_mesh_smooth_run")
+        out_n = None if normals is None else _vertex_normals(lib, out, faces_in, n_vertices, n_faces, dev)
+        n_edges, n_boundary = counts.tolist()                           # the one host read
+    return out, faces, out_n, MeshSmoothStats(n_edges, n_boundary, n_boundary if fix_boundary else 0, iterations * (2 if mu != 0.0 else 1))
+
+
 # ---------------------------------------------------------------------------------------- sparse evaluation of a dense grid
 class SparseGridStats(NamedTuple):
     bricks: int                                  # bricks of the grid

@@ -746,6 +746,33 @@ int nf_mesh_components_emit(const float* vertices, const int* faces, const float
                             size_t workspace_bytes, float* out_vertices, int64_t cap_vertices, int* out_faces, int64_t cap_faces,
                             float* out_normals, nf_stream_t stream);
 
+/* ---- Taubin smoothing of an indexed mesh, and the vertex normals of its faces (ABI 5 still: these only add) ------------------------
+ * vertices: f32 [V][3], faces: int32 [F][3], 0 <= V < 2^31 and 0 <= 6 F < 2^31 (DESIGN.md "Mesh smoothing" is the specification).  A
+ * face is valid iff its three indices lie in [0, V); a valid face (a, b, c) has the sides ab, bc, ca, a side with equal ends is
+ * dropped.  workspace: nf_mesh_smooth_workspace_bytes(V, F) bytes, 8-byte aligned, any content; 0 = a size that is not served.
+ *   nf_mesh_smooth_adjacency  the neighbours of every vertex as CSR: row_start[V + 1]; neighbours / multiplicity: buffers of 6 F
+ *                             entries of which the first E are written -- row v holds the distinct w != v joined to v by a side,
+ *                             ascending, and the number of sides joining them; boundary[V] = 1 iff v ends an edge of multiplicity
+ *                             1; counts_dev[0] = E, counts_dev[1] = boundary vertices (int64, on the device).
+ *   nf_mesh_smooth_run        iterations x (a pass with lam, then, unless mu == 0, a pass with mu) over a table of
+ *                             nf_mesh_smooth_adjacency, all enqueued by this one call: p'[v] = p[v] + f * (mean of p over N(v) - p[v])
+ *                             with the sum in ascending neighbour order and every operation rounded on its own; a vertex without
+ *                             neighbours, or with pinned[v] != 0 (pinned: NULL = none), is copied.  The passes alternate between
+ *                             tmp and out (V x 3 floats each; tmp may be NULL for at most one pass), the result is in out;
+ *                             iterations == 0 copies.  vertices, tmp and out are three different buffers.
+ *   nf_mesh_smooth_normals    normals[V][3]: the sum of (p[b] - p[a]) x (p[c] - p[a]) over the valid faces that hold the vertex, each
+ *                             once, in ascending face order, divided by its length; the zero vector where that is zero or not finite.
+ * NF_EINVAL before any device call: NULL pointers where the size is not 0, an unserved size, workspace_bytes too small, negative
+ * iterations, lam outside (0, 1], mu outside [-1, 0], either not a number, aliased buffers.  No float atomics: two calls give the same bits. */
+size_t nf_mesh_smooth_workspace_bytes(int64_t n_vertices, int64_t n_faces);
+int nf_mesh_smooth_adjacency(const int* faces, int64_t n_vertices, int64_t n_faces, void* workspace, size_t workspace_bytes,
+                             int* row_start, int* neighbours, int* multiplicity, uint8_t* boundary, int64_t* counts_dev,
+                             nf_stream_t stream);
+int nf_mesh_smooth_run(const float* vertices, int64_t n_vertices, const int* row_start, const int* neighbours, const uint8_t* pinned,
+                       int iterations, float lam, float mu, float* tmp, float* out, nf_stream_t stream);
+int nf_mesh_smooth_normals(const float* vertices, const int* faces, int64_t n_vertices, int64_t n_faces, void* workspace,
+                           size_t workspace_bytes, float* normals, nf_stream_t stream);
+
 /* ---- host-only self-tests (no device needed): consistency of the weight-gradient job tables -- every slab entry written
  * exactly once per slice, tile ids inside their bundle.  0 = consistent, negative = which check failed.                 */
 int nf_selftest_dw_tables_f32(void);
