@@ -16,7 +16,7 @@
 // Four launches, one thread per grid point (a cell is the point at its corner 0), 256 points per workgroup, no atomics:
 //   nf_isosurface_count: k_iso_count  corner values -> inside bits (1 B) and crossing mask (1 B) per point; per-workgroup sums of
 //                                     vertices and triangles
-//                        k_iso_scan   one workgroup: exclusive scan of the per-workgroup sums in place; V and F
+//                        k_iso_scan   one workgroup: both arrays of sums -> exclusive prefixes (nf_scan_dev.h); V and F
 //   nf_isosurface_emit:  k_iso_verts  crossing mask -> wave64 / workgroup scan -> vbase[point]; positions (and normals) of the
 //                                     point's own edges
 //                        k_iso_faces  inside bits -> triangles per cell -> scan -> face base; indices from vbase / mask of the owners
@@ -25,12 +25,7 @@
 #include "nf_grid_dev.h"
 
 namespace nfi {
-constexpr int THREADS = 256;               // points per workgroup (4 waves), one block sum each (1024 was measured too: DESIGN.md)
-constexpr int WAVES = THREADS / NF_WAVE;
-constexpr int SCAN_THREADS = 1024;         // k_iso_scan: its one workgroup
-constexpr int SCAN_WAVES = SCAN_THREADS / NF_WAVE;
-constexpr int HEADER = 256;                // bytes: V, F as int64 at the workspace's start
-constexpr int SCAN_PER_THREAD = 16;        // k_iso_scan: block sums per thread and round
+constexpr int SCAN_PER_THREAD = 16;        // k_iso_scan: block sums per thread and round.  The header: V, F
 
 // ---- the case table, derived at compile time (host and device see the same constant expression)
 constexpr int PERM[6][3] = {{0, 1, 2}, {0, 2, 1}, {1, 0, 2}, {1, 2, 0}, {2, 0, 1}, {2, 1, 0}};   // lexicographic
@@ -137,25 +132,19 @@ struct NfIsoPlan {
     size_t off_block_v, off_block_f, off_vbase, off_mask, off_inside, bytes;
 };
 
-static inline size_t nf_iso_up(size_t b) { return (b + 255) / 256 * 256; }
-
-// false: a size the plan does not support.  V <= 7 points and F <= 12 cells are bounded BEFORE any launch, so every count and
-// every prefix fits 31 bits.
+// false: a grid the plan does not serve (nf_grid_points)
 static inline bool nf_iso_plan(int nx, int ny, int nz, NfIsoPlan* p) {
-    if (nx < 2 || ny < 2 || nz < 2) return false;
-    if ((int64_t)nx * ny > 0x7fffffff) return false;            // the product is checked stepwise: no 64-bit overflow
-    const int64_t n = (int64_t)nx * ny * nz;
-    const int64_t cells = (int64_t)(nx - 1) * (ny - 1) * (nz - 1);
-    if (7 * n > 0x7fffffff || 12 * cells > 0x7fffffff) return false;
+    const int64_t n = nf_grid_points(nx, ny, nz);
+    if (!n) return false;
     p->n_points = n;
-    p->n_blocks = (n + nfi::THREADS - 1) / nfi::THREADS;
-    size_t at = nfi::HEADER;
-    p->off_block_v = at, at += nf_iso_up((size_t)p->n_blocks * 4);
-    p->off_block_f = at, at += nf_iso_up((size_t)p->n_blocks * 4);
-    p->off_vbase = at, at += nf_iso_up((size_t)n * 4);
-    p->off_mask = at, at += nf_iso_up((size_t)n);
-    p->off_inside = at, at += nf_iso_up((size_t)n);
-    p->bytes = at;
+    p->n_blocks = nf_blocks(n);
+    NfWorkspace ws;
+    p->off_block_v = ws.take((size_t)p->n_blocks * 4);
+    p->off_block_f = ws.take((size_t)p->n_blocks * 4);
+    p->off_vbase = ws.take((size_t)n * 4);
+    p->off_mask = ws.take((size_t)n);
+    p->off_inside = ws.take((size_t)n);
+    p->bytes = ws.at;
     return true;
 }
 
@@ -164,7 +153,7 @@ extern "C" size_t nf_isosurface_workspace_bytes(int nx, int ny, int nz) {
     return nf_iso_plan(nx, ny, nz, &p) ? p.bytes : 0;
 }
 
-// ---- device helpers (the workgroup scan nf_iso_block_scan and the index split nf_iso_point: nf_grid_dev.h)
+// ---- device helpers (the workgroup scan nf_block_scan: nf_scan_dev.h; the index split nf_iso_point: nf_grid_dev.h)
 // triangles of a cell from the inside bits of its eight corners: per tetrahedron 1 for one or three corners inside, 2 for two (the
 // table's own counts, without a per-lane table read for every point of the grid)
 __device__ __forceinline__ uint32_t nf_iso_cell_tris(uint32_t inside) {
@@ -177,11 +166,11 @@ __device__ __forceinline__ uint32_t nf_iso_cell_tris(uint32_t inside) {
     return n;
 }
 
-__global__ void __launch_bounds__(nfi::THREADS) k_iso_count(const float* __restrict__ grid, int nx, int ny, int nz, float level, int64_t n_points,
+__global__ void __launch_bounds__(nfc::THREADS) k_iso_count(const float* __restrict__ grid, int nx, int ny, int nz, float level, int64_t n_points,
                                                             uint8_t* __restrict__ mask_out, uint8_t* __restrict__ inside_out,
                                                             uint32_t* __restrict__ block_v, uint32_t* __restrict__ block_f) {
-    __shared__ uint32_t s_wave[nfi::WAVES];
-    const int64_t p = (int64_t)blockIdx.x * nfi::THREADS + threadIdx.x;
+    __shared__ uint32_t s_wave[nfc::WAVES];
+    const int64_t p = (int64_t)blockIdx.x * nfc::THREADS + threadIdx.x;
     uint32_t n_vert = 0, n_tri = 0;
     if (p < n_points) {
         const NfIsoPoint g = nf_iso_point(p, nx, ny);
@@ -205,8 +194,8 @@ __global__ void __launch_bounds__(nfi::THREADS) k_iso_count(const float* __restr
         mask_out[p] = (uint8_t)mask;
         inside_out[p] = cell ? (uint8_t)inside : (uint8_t)0;       // a point that is no cell's corner 0 reads as an empty cell
     }
-    uint32_t total;                                                 // both sums in one pass: <= 7 * 256 vertices below, <= 12 * 256 triangles above bit 16
-    nf_iso_block_scan<nfi::WAVES>(n_vert | n_tri << 16, s_wave, &total);
+    // both sums in one pass: <= 7 * 256 vertices below, <= 12 * 256 triangles above bit 16
+    const uint32_t total = nf_block_total<nfc::WAVES>(n_vert | n_tri << 16, s_wave);
     if (threadIdx.x == 0) {
         block_v[blockIdx.x] = total & 0xffffu;
         block_f[blockIdx.x] = total >> 16;
@@ -214,37 +203,17 @@ __global__ void __launch_bounds__(nfi::THREADS) k_iso_count(const float* __restr
 }
 
 // one workgroup: both arrays of block sums -> exclusive prefixes in place, the totals to the header and to counts_out
-__global__ void __launch_bounds__(nfi::SCAN_THREADS) k_iso_scan(uint32_t* __restrict__ block_v, uint32_t* __restrict__ block_f, int64_t n_blocks,
+__global__ void __launch_bounds__(nfc::SCAN_THREADS) k_iso_scan(uint32_t* __restrict__ block_v, uint32_t* __restrict__ block_f, int64_t n_blocks,
                                                            long long* __restrict__ header, long long* __restrict__ counts_out) {
-    __shared__ uint32_t s_wave[nfi::SCAN_WAVES];
+    __shared__ uint32_t s_wave[nfc::SCAN_WAVES];
     for (int which = 0; which < 2; ++which) {
-        uint32_t* a = which ? block_f : block_v;
-        uint32_t carry = 0;
-        for (int64_t base = 0; base < n_blocks; base += (int64_t)nfi::SCAN_THREADS * nfi::SCAN_PER_THREAD) {
-            const int64_t at = base + (int64_t)threadIdx.x * nfi::SCAN_PER_THREAD;
-            uint32_t v[nfi::SCAN_PER_THREAD], sum = 0;                  // unrolled: registers, constant indices only
-#pragma unroll
-            for (int q = 0; q < nfi::SCAN_PER_THREAD; ++q) {
-                v[q] = at + q < n_blocks ? a[at + q] : 0u;
-                sum += v[q];
-            }
-            uint32_t total;
-            uint32_t run = carry + nf_iso_block_scan<nfi::SCAN_WAVES>(sum, s_wave, &total) - sum;
-#pragma unroll
-            for (int q = 0; q < nfi::SCAN_PER_THREAD; ++q) {
-                if (at + q < n_blocks) a[at + q] = run;
-                run += v[q];
-            }
-            carry += total;
-        }
+        const uint32_t carry = nf_scan_block_sums<nfi::SCAN_PER_THREAD>(which ? block_f : block_v, n_blocks, s_wave);
         if (threadIdx.x == 0) {
             header[which] = (long long)carry;
             counts_out[which] = (long long)carry;
         }
     }
 }
-
-struct NfIsoBox { float lo[3], h[3]; };
 
 // central difference of the grid along one axis at index a (stride s), one-sided at the box faces, divided by the spacing
 __device__ __forceinline__ float nf_iso_diff(const float* __restrict__ grid, int64_t p, int a, int n, int64_t s, float h) {
@@ -253,26 +222,26 @@ __device__ __forceinline__ float nf_iso_diff(const float* __restrict__ grid, int
     return nf_div(nf_sub(grid[up], grid[dn]), span);
 }
 
-__global__ void __launch_bounds__(nfi::THREADS) k_iso_verts(const float* __restrict__ grid, int nx, int ny, int nz, float level, int64_t n_points,
-                                                            NfIsoBox box, const uint8_t* __restrict__ mask_in,
+__global__ void __launch_bounds__(nfc::THREADS) k_iso_verts(const float* __restrict__ grid, int nx, int ny, int nz, float level, int64_t n_points,
+                                                            NfGridBox box, const uint8_t* __restrict__ mask_in,
                                                             const uint32_t* __restrict__ block_v, uint32_t* __restrict__ vbase_out,
                                                             float* __restrict__ verts, int64_t cap_verts, float* __restrict__ normals) {
-    __shared__ uint32_t s_wave[nfi::WAVES];
-    const int64_t p = (int64_t)blockIdx.x * nfi::THREADS + threadIdx.x;
+    __shared__ uint32_t s_wave[nfc::WAVES];
+    const int64_t p = (int64_t)blockIdx.x * nfc::THREADS + threadIdx.x;
     const uint32_t mask = p < n_points ? mask_in[p] : 0u;
     const uint32_t n_vert = __popc(mask);
     uint32_t total;
-    const uint32_t base = block_v[blockIdx.x] + nf_iso_block_scan<nfi::WAVES>(n_vert, s_wave, &total) - n_vert;
+    const uint32_t base = block_v[blockIdx.x] + nf_block_scan<nfc::WAVES>(n_vert, s_wave, &total) - n_vert;
     if (p >= n_points) return;
     vbase_out[p] = base;
     if (!mask) return;
     const NfIsoPoint g = nf_iso_point(p, nx, ny);
     const int64_t sy = nx, sz = (int64_t)nx * ny;
     const float va = grid[p];
-    const float pa_x = nf_add(box.lo[0], nf_mul((float)g.i, box.h[0])), pa_y = nf_add(box.lo[1], nf_mul((float)g.j, box.h[1])),
-                pa_z = nf_add(box.lo[2], nf_mul((float)g.k, box.h[2]));
-    const float pb_x = nf_add(box.lo[0], nf_mul((float)(g.i + 1), box.h[0])), pb_y = nf_add(box.lo[1], nf_mul((float)(g.j + 1), box.h[1])),
-                pb_z = nf_add(box.lo[2], nf_mul((float)(g.k + 1), box.h[2]));
+    const float pa_x = nf_grid_coord(box.lo[0], box.h[0], g.i), pa_y = nf_grid_coord(box.lo[1], box.h[1], g.j),
+                pa_z = nf_grid_coord(box.lo[2], box.h[2], g.k);
+    const float pb_x = nf_grid_coord(box.lo[0], box.h[0], g.i + 1), pb_y = nf_grid_coord(box.lo[1], box.h[1], g.j + 1),
+                pb_z = nf_grid_coord(box.lo[2], box.h[2], g.k + 1);
     float ga_x = 0.f, ga_y = 0.f, ga_z = 0.f;
     if (normals) {
         ga_x = nf_iso_diff(grid, p, g.i, nx, 1, box.h[0]);
@@ -308,15 +277,15 @@ __global__ void __launch_bounds__(nfi::THREADS) k_iso_verts(const float* __restr
     }
 }
 
-__global__ void __launch_bounds__(nfi::THREADS) k_iso_faces(int nx, int ny, int64_t n_points, const uint8_t* __restrict__ mask_in,
+__global__ void __launch_bounds__(nfc::THREADS) k_iso_faces(int nx, int ny, int64_t n_points, const uint8_t* __restrict__ mask_in,
                                                             const uint8_t* __restrict__ inside_in, const uint32_t* __restrict__ vbase,
                                                             const uint32_t* __restrict__ block_f, int* __restrict__ faces, int64_t cap_faces) {
-    __shared__ uint32_t s_wave[nfi::WAVES];
-    const int64_t p = (int64_t)blockIdx.x * nfi::THREADS + threadIdx.x;
+    __shared__ uint32_t s_wave[nfc::WAVES];
+    const int64_t p = (int64_t)blockIdx.x * nfc::THREADS + threadIdx.x;
     const uint32_t inside = p < n_points ? inside_in[p] : 0u;       // 0 where the point is no cell (k_iso_count)
     const uint32_t n_tri = nf_iso_cell_tris(inside);
     uint32_t total;
-    int64_t f = (int64_t)block_f[blockIdx.x] + nf_iso_block_scan<nfi::WAVES>(n_tri, s_wave, &total) - n_tri;
+    int64_t f = (int64_t)block_f[blockIdx.x] + nf_block_scan<nfc::WAVES>(n_tri, s_wave, &total) - n_tri;
     if (!n_tri) return;
     const int64_t sy = nx, sz = (int64_t)nx * ny;
 #pragma unroll
@@ -349,9 +318,9 @@ extern "C" int nf_isosurface_count(const float* grid, int nx, int ny, int nz, fl
     char* ws = static_cast<char*>(workspace);
     uint32_t* block_v = reinterpret_cast<uint32_t*>(ws + p.off_block_v);
     uint32_t* block_f = reinterpret_cast<uint32_t*>(ws + p.off_block_f);
-    hipLaunchKernelGGL(k_iso_count, dim3((unsigned)p.n_blocks), dim3(nfi::THREADS), 0, nf_s(stream), grid, nx, ny, nz, level, p.n_points,
+    hipLaunchKernelGGL(k_iso_count, dim3((unsigned)p.n_blocks), dim3(nfc::THREADS), 0, nf_s(stream), grid, nx, ny, nz, level, p.n_points,
                        reinterpret_cast<uint8_t*>(ws + p.off_mask), reinterpret_cast<uint8_t*>(ws + p.off_inside), block_v, block_f);
-    hipLaunchKernelGGL(k_iso_scan, dim3(1), dim3(nfi::SCAN_THREADS), 0, nf_s(stream), block_v, block_f, p.n_blocks, reinterpret_cast<long long*>(ws),
+    hipLaunchKernelGGL(k_iso_scan, dim3(1), dim3(nfc::SCAN_THREADS), 0, nf_s(stream), block_v, block_f, p.n_blocks, reinterpret_cast<long long*>(ws),
                        reinterpret_cast<long long*>(counts_dev));
     NF_RETURN_LAUNCH();
 }
@@ -362,19 +331,14 @@ extern "C" int nf_isosurface_emit(const float* grid, int nx, int ny, int nz, flo
     NfIsoPlan p;
     if (!grid || !workspace || !lo || !hi || !verts || !faces || !nf_iso_plan(nx, ny, nz, &p) || workspace_bytes < p.bytes) return NF_EINVAL;
     if (n_verts < 0 || n_faces < 0 || n_verts > 0x7fffffff || n_faces > 0x7fffffff) return NF_EINVAL;
-    const int n[3] = {nx, ny, nz};
-    NfIsoBox box;
-    for (int a = 0; a < 3; ++a) {
-        if (!(lo[a] < hi[a])) return NF_EINVAL;                     // NaN bounds too
-        box.lo[a] = lo[a];
-        box.h[a] = (hi[a] - lo[a]) / (float)(n[a] - 1);
-    }
+    NfGridBox box;
+    if (!nf_grid_box(lo, hi, nx, ny, nz, &box)) return NF_EINVAL;
     char* ws = static_cast<char*>(workspace);
     const uint8_t* mask = reinterpret_cast<const uint8_t*>(ws + p.off_mask);
     uint32_t* vbase = reinterpret_cast<uint32_t*>(ws + p.off_vbase);
-    hipLaunchKernelGGL(k_iso_verts, dim3((unsigned)p.n_blocks), dim3(nfi::THREADS), 0, nf_s(stream), grid, nx, ny, nz, level, p.n_points, box, mask,
+    hipLaunchKernelGGL(k_iso_verts, dim3((unsigned)p.n_blocks), dim3(nfc::THREADS), 0, nf_s(stream), grid, nx, ny, nz, level, p.n_points, box, mask,
                        reinterpret_cast<const uint32_t*>(ws + p.off_block_v), vbase, verts, n_verts, normals);
-    hipLaunchKernelGGL(k_iso_faces, dim3((unsigned)p.n_blocks), dim3(nfi::THREADS), 0, nf_s(stream), nx, ny, p.n_points, mask,
+    hipLaunchKernelGGL(k_iso_faces, dim3((unsigned)p.n_blocks), dim3(nfc::THREADS), 0, nf_s(stream), nx, ny, p.n_points, mask,
                        reinterpret_cast<const uint8_t*>(ws + p.off_inside), vbase, reinterpret_cast<const uint32_t*>(ws + p.off_block_f), faces,
                        n_faces);
     NF_RETURN_LAUNCH();

@@ -15,7 +15,7 @@
 //   nf_mesh_components_label:  k_mc_init     parent[v] = v
 //                              k_mc_hook     valid face (a, b, c): union(a, b), union(a, c)
 //                              k_mc_flatten  parent[v] = find(v); per-workgroup number of roots
-//                              k_mc_scan     one workgroup: exclusive scan of the block sums in place; C
+//                              k_mc_scan     one workgroup: the block sums -> exclusive prefixes (nf_scan_dev.h); C
 //                              k_mc_rank     roots: vertex_label[root] = its rank (the numbering rule); the counts of that rank = 0
 //                              k_mc_labels   the other vertices and the faces take their root's rank; counts by integer atomicAdd
 //   nf_mesh_components_select: k_mc_select   one workgroup: the argmax of face_counts (largest) and the number of kept components
@@ -25,22 +25,18 @@
 //                              k_mc_emit_faces  scan -> row of every kept face; indices through the new ids
 // Integer sums only, in a fixed order or by integer atomics: two calls give the same bits.  The workspace may arrive with any
 // content: every word a kernel reads was written by an earlier kernel of the same call chain.
-#include "nf_grid_dev.h"
+#include "nf_mesh_dev.h"
+#include "nf_scan_dev.h"
 
 namespace nfm {
-constexpr int THREADS = 256;               // vertices or faces per workgroup (4 waves), one block sum each
-constexpr int WAVES = THREADS / NF_WAVE;
-constexpr int SCAN_THREADS = 1024;         // k_mc_scan and k_mc_select: their one workgroup
-constexpr int SCAN_WAVES = SCAN_THREADS / NF_WAVE;
 constexpr int SCAN_PER_THREAD = 4;         // k_mc_scan: block sums per thread and round (a round takes 4096 sums: 2^20 vertices)
-constexpr int HEADER = 256;                // bytes at the workspace's start: NfMcHeader
 
-struct Header {
+struct Header {                            // the workspace's start
     long long components, kept_vertices, kept_faces, kept_components;
     long long min_faces;                   // the rule k_mc_select was given: largest (best_label) or min_faces >= 1
     int largest, best_label;               // best_label: -1 = keep nothing
 };
-static_assert(sizeof(Header) <= HEADER, "the header has 256 bytes");
+static_assert(sizeof(Header) <= nfc::HEADER, "the header has 256 bytes");
 }  // namespace nfm
 
 // ---- workspace plan
@@ -49,19 +45,17 @@ struct NfMcPlan {
     size_t off_parent, off_new_id, off_block_v, off_block_f, bytes;
 };
 
-static inline size_t nf_mc_up(size_t b) { return (b + 255) / 256 * 256; }
-
 // false: a size the plan does not serve.  V and F stay below 2^31 (ids and counts are int32); either may be 0.
 static inline bool nf_mc_plan(int64_t n_vertices, int64_t n_faces, NfMcPlan* p) {
     if (n_vertices < 0 || n_faces < 0 || n_vertices > 0x7fffffff || n_faces > 0x7fffffff) return false;
-    p->blocks_v = (n_vertices + nfm::THREADS - 1) / nfm::THREADS;
-    p->blocks_f = (n_faces + nfm::THREADS - 1) / nfm::THREADS;
-    size_t at = nfm::HEADER;
-    p->off_parent = at, at += nf_mc_up((size_t)n_vertices * 4);
-    p->off_new_id = at, at += nf_mc_up((size_t)n_vertices * 4);
-    p->off_block_v = at, at += nf_mc_up((size_t)p->blocks_v * 4);
-    p->off_block_f = at, at += nf_mc_up((size_t)p->blocks_f * 4);
-    p->bytes = at;
+    p->blocks_v = nf_blocks(n_vertices);
+    p->blocks_f = nf_blocks(n_faces);
+    NfWorkspace ws;
+    p->off_parent = ws.take((size_t)n_vertices * 4);
+    p->off_new_id = ws.take((size_t)n_vertices * 4);
+    p->off_block_v = ws.take((size_t)p->blocks_v * 4);
+    p->off_block_f = ws.take((size_t)p->blocks_f * 4);
+    p->bytes = ws.at;
     return true;
 }
 
@@ -100,25 +94,15 @@ __device__ __forceinline__ void nf_mc_union(int* __restrict__ parent, int a, int
     }
 }
 
-// the three indices of face f (64-bit addressing: 3 * F passes 2^31) and whether all lie in [0, V)
-struct NfMcFace { int a, b, c; bool valid; };
-
-__device__ __forceinline__ NfMcFace nf_mc_face(const int* __restrict__ faces, int64_t f, int64_t n_vertices) {
-    NfMcFace t;
-    t.a = faces[f * 3 + 0], t.b = faces[f * 3 + 1], t.c = faces[f * 3 + 2];
-    t.valid = t.a >= 0 && t.a < n_vertices && t.b >= 0 && t.b < n_vertices && t.c >= 0 && t.c < n_vertices;
-    return t;
-}
-
-__global__ void __launch_bounds__(nfm::THREADS) k_mc_init(int* __restrict__ parent, int64_t n_vertices) {
-    const int64_t v = (int64_t)blockIdx.x * nfm::THREADS + threadIdx.x;
+__global__ void __launch_bounds__(nfc::THREADS) k_mc_init(int* __restrict__ parent, int64_t n_vertices) {
+    const int64_t v = (int64_t)blockIdx.x * nfc::THREADS + threadIdx.x;
     if (v < n_vertices) parent[v] = (int)v;
 }
 
-__global__ void __launch_bounds__(nfm::THREADS) k_mc_hook(const int* __restrict__ faces, int64_t n_vertices, int64_t n_faces, int* __restrict__ parent) {
-    const int64_t f = (int64_t)blockIdx.x * nfm::THREADS + threadIdx.x;
+__global__ void __launch_bounds__(nfc::THREADS) k_mc_hook(const int* __restrict__ faces, int64_t n_vertices, int64_t n_faces, int* __restrict__ parent) {
+    const int64_t f = (int64_t)blockIdx.x * nfc::THREADS + threadIdx.x;
     if (f >= n_faces) return;
-    const NfMcFace t = nf_mc_face(faces, f, n_vertices);            // range-checked before anything is indexed
+    const NfFace t = nf_face(faces, f, n_vertices);                 // range-checked before anything is indexed
     if (!t.valid) return;
     // two vertices with the same parent are joined already (a parent lies in its child's set): no find, which would end in a read
     // of the root's word -- in a mesh of one component the same word for every face
@@ -129,45 +113,25 @@ __global__ void __launch_bounds__(nfm::THREADS) k_mc_hook(const int* __restrict_
 
 // parent[v] = the root of v (no hook runs any more, so a root stays one; other threads' halving and this store only lower
 // parent[], towards the same root); the number of roots per workgroup
-__global__ void __launch_bounds__(nfm::THREADS) k_mc_flatten(int* __restrict__ parent, int64_t n_vertices, uint32_t* __restrict__ block_v) {
-    __shared__ uint32_t s_wave[nfm::WAVES];
-    const int64_t v = (int64_t)blockIdx.x * nfm::THREADS + threadIdx.x;
+__global__ void __launch_bounds__(nfc::THREADS) k_mc_flatten(int* __restrict__ parent, int64_t n_vertices, uint32_t* __restrict__ block_v) {
+    __shared__ uint32_t s_wave[nfc::WAVES];
+    const int64_t v = (int64_t)blockIdx.x * nfc::THREADS + threadIdx.x;
     uint32_t is_root = 0;
     if (v < n_vertices) {
         const int r = nf_mc_find(parent, (int)v);
         if (r != (int)v) atomicMin(parent + v, r);
         is_root = r == (int)v ? 1u : 0u;
     }
-    uint32_t total;
-    nf_iso_block_scan<nfm::WAVES>(is_root, s_wave, &total);
+    const uint32_t total = nf_block_total<nfc::WAVES>(is_root, s_wave);
     if (threadIdx.x == 0) block_v[blockIdx.x] = total;
 }
 
 // one workgroup: up to two arrays of block sums -> exclusive prefixes in place; their totals to header[slot] and counts_out[slot]
-__global__ void __launch_bounds__(nfm::SCAN_THREADS) k_mc_scan(uint32_t* __restrict__ a0, int64_t n0, int slot0, uint32_t* __restrict__ a1, int64_t n1,
+__global__ void __launch_bounds__(nfc::SCAN_THREADS) k_mc_scan(uint32_t* __restrict__ a0, int64_t n0, int slot0, uint32_t* __restrict__ a1, int64_t n1,
                                                           int slot1, int n_arrays, long long* __restrict__ header, long long* __restrict__ counts_out) {
-    __shared__ uint32_t s_wave[nfm::SCAN_WAVES];
+    __shared__ uint32_t s_wave[nfc::SCAN_WAVES];
     for (int which = 0; which < n_arrays; ++which) {
-        uint32_t* a = which ? a1 : a0;
-        const int64_t n_blocks = which ? n1 : n0;
-        uint32_t carry = 0;
-        for (int64_t base = 0; base < n_blocks; base += (int64_t)nfm::SCAN_THREADS * nfm::SCAN_PER_THREAD) {
-            const int64_t at = base + (int64_t)threadIdx.x * nfm::SCAN_PER_THREAD;
-            uint32_t v[nfm::SCAN_PER_THREAD], sum = 0;
-#pragma unroll
-            for (int q = 0; q < nfm::SCAN_PER_THREAD; ++q) {
-                v[q] = at + q < n_blocks ? a[at + q] : 0u;
-                sum += v[q];
-            }
-            uint32_t total;
-            uint32_t run = carry + nf_iso_block_scan<nfm::SCAN_WAVES>(sum, s_wave, &total) - sum;
-#pragma unroll
-            for (int q = 0; q < nfm::SCAN_PER_THREAD; ++q) {
-                if (at + q < n_blocks) a[at + q] = run;
-                run += v[q];
-            }
-            carry += total;
-        }
+        const uint32_t carry = nf_scan_block_sums<nfm::SCAN_PER_THREAD>(which ? a1 : a0, which ? n1 : n0, s_wave);
         if (threadIdx.x == 0) {
             const int slot = which ? slot1 : slot0;
             header[slot] = (long long)carry;
@@ -177,13 +141,13 @@ __global__ void __launch_bounds__(nfm::SCAN_THREADS) k_mc_scan(uint32_t* __restr
 }
 
 // a root's label is the number of roots below it; the two counts of that label start at 0 (labels >= C are never written)
-__global__ void __launch_bounds__(nfm::THREADS) k_mc_rank(const int* __restrict__ parent, int64_t n_vertices, const uint32_t* __restrict__ block_v,
+__global__ void __launch_bounds__(nfc::THREADS) k_mc_rank(const int* __restrict__ parent, int64_t n_vertices, const uint32_t* __restrict__ block_v,
                                                           int* __restrict__ vertex_label, int* __restrict__ face_counts, int* __restrict__ vertex_counts) {
-    __shared__ uint32_t s_wave[nfm::WAVES];
-    const int64_t v = (int64_t)blockIdx.x * nfm::THREADS + threadIdx.x;
+    __shared__ uint32_t s_wave[nfc::WAVES];
+    const int64_t v = (int64_t)blockIdx.x * nfc::THREADS + threadIdx.x;
     const uint32_t is_root = v < n_vertices && parent[v] == (int)v ? 1u : 0u;
     uint32_t total;
-    const uint32_t rank = block_v[blockIdx.x] + nf_iso_block_scan<nfm::WAVES>(is_root, s_wave, &total) - is_root;
+    const uint32_t rank = block_v[blockIdx.x] + nf_block_scan<nfc::WAVES>(is_root, s_wave, &total) - is_root;
     if (!is_root) return;
     vertex_label[v] = (int)rank;
     face_counts[rank] = 0;
@@ -197,7 +161,7 @@ __device__ __forceinline__ void nf_mc_count_runs(int* __restrict__ counts, int l
     if (threadIdx.x == 0) *s_first = label;
     __syncthreads();
     if (__syncthreads_and(label == *s_first)) {                    // the whole workgroup in one component: one add
-        if (threadIdx.x == 0 && label >= 0) atomicAdd(counts + label, nfm::THREADS);
+        if (threadIdx.x == 0 && label >= 0) atomicAdd(counts + label, nfc::THREADS);
         return;
     }
     const int lane = threadIdx.x & 63;
@@ -210,13 +174,13 @@ __device__ __forceinline__ void nf_mc_count_runs(int* __restrict__ counts, int l
 }
 
 // workgroups [0, blocks_v): vertices, the rest: faces.  Both read the labels of ROOTS only, which k_mc_rank wrote.
-__global__ void __launch_bounds__(nfm::THREADS) k_mc_labels(const int* __restrict__ faces, const int* __restrict__ parent, int64_t n_vertices, int64_t n_faces,
+__global__ void __launch_bounds__(nfc::THREADS) k_mc_labels(const int* __restrict__ faces, const int* __restrict__ parent, int64_t n_vertices, int64_t n_faces,
                                                             int64_t blocks_v, int* __restrict__ vertex_label, int* __restrict__ face_label,
                                                             int* __restrict__ face_counts, int* __restrict__ vertex_counts) {
     __shared__ int s_first;
     int label = -1;
     if ((int64_t)blockIdx.x < blocks_v) {
-        const int64_t v = (int64_t)blockIdx.x * nfm::THREADS + threadIdx.x;
+        const int64_t v = (int64_t)blockIdx.x * nfc::THREADS + threadIdx.x;
         if (v < n_vertices) {
             const int root = parent[v];
             label = vertex_label[root];
@@ -224,9 +188,9 @@ __global__ void __launch_bounds__(nfm::THREADS) k_mc_labels(const int* __restric
         }
         nf_mc_count_runs(vertex_counts, label, &s_first);
     } else {
-        const int64_t f = ((int64_t)blockIdx.x - blocks_v) * nfm::THREADS + threadIdx.x;
+        const int64_t f = ((int64_t)blockIdx.x - blocks_v) * nfc::THREADS + threadIdx.x;
         if (f < n_faces) {
-            const NfMcFace t = nf_mc_face(faces, f, n_vertices);
+            const NfFace t = nf_face(faces, f, n_vertices);
             if (t.valid) label = vertex_label[parent[t.a]];
             face_label[f] = label;
         }
@@ -241,14 +205,14 @@ __device__ __forceinline__ bool nf_mc_keeps(const nfm::Header* __restrict__ h, c
 
 // one workgroup over the C components: the largest count and its lowest label (key = count << 32 | ~label, maximised), the number of
 // components the rule keeps; the rule itself goes to the header, where k_mc_keep and the emit kernels read it
-__global__ void __launch_bounds__(nfm::SCAN_THREADS) k_mc_select(const int* __restrict__ face_counts, int largest, long long min_faces,
+__global__ void __launch_bounds__(nfc::SCAN_THREADS) k_mc_select(const int* __restrict__ face_counts, int largest, long long min_faces,
                                                             nfm::Header* __restrict__ header, long long* __restrict__ counts_out) {
-    __shared__ unsigned long long s_key[nfm::SCAN_WAVES];
-    __shared__ uint32_t s_wave[nfm::SCAN_WAVES];
+    __shared__ unsigned long long s_key[nfc::SCAN_WAVES];
+    __shared__ uint32_t s_wave[nfc::SCAN_WAVES];
     const long long n = header->components;
     unsigned long long key = 0;
     uint32_t kept = 0;
-    for (long long c = threadIdx.x; c < n; c += nfm::SCAN_THREADS) {
+    for (long long c = threadIdx.x; c < n; c += nfc::SCAN_THREADS) {
         const int count = face_counts[c];
         const unsigned long long k = (unsigned long long)(uint32_t)count << 32 | (uint32_t)~(uint32_t)c;
         key = k > key ? k : key;
@@ -258,12 +222,11 @@ __global__ void __launch_bounds__(nfm::SCAN_THREADS) k_mc_select(const int* __re
         const unsigned long long other = __shfl_xor(key, o, 64);
         key = other > key ? other : key;
     }
-    uint32_t total;
-    nf_iso_block_scan<nfm::SCAN_WAVES>(kept, s_wave, &total);
+    const uint32_t total = nf_block_total<nfc::SCAN_WAVES>(kept, s_wave);
     if ((threadIdx.x & 63) == 0) s_key[threadIdx.x >> 6] = key;
     __syncthreads();
     if (threadIdx.x == 0) {
-        for (int w = 1; w < nfm::SCAN_WAVES; ++w) key = s_key[w] > key ? s_key[w] : key;
+        for (int w = 1; w < nfc::SCAN_WAVES; ++w) key = s_key[w] > key ? s_key[w] : key;
         const bool any = (key >> 32) != 0;                          // some component has a face
         header->largest = largest;
         header->min_faces = min_faces;
@@ -275,35 +238,34 @@ __global__ void __launch_bounds__(nfm::SCAN_THREADS) k_mc_select(const int* __re
 }
 
 // workgroups [0, blocks_v): kept vertices per workgroup, the rest: kept faces per workgroup
-__global__ void __launch_bounds__(nfm::THREADS) k_mc_keep(const int* __restrict__ vertex_label, const int* __restrict__ face_label,
+__global__ void __launch_bounds__(nfc::THREADS) k_mc_keep(const int* __restrict__ vertex_label, const int* __restrict__ face_label,
                                                           const int* __restrict__ face_counts, int64_t n_vertices, int64_t n_faces, int64_t blocks_v,
                                                           const nfm::Header* __restrict__ header, uint32_t* __restrict__ block_v,
                                                           uint32_t* __restrict__ block_f) {
-    __shared__ uint32_t s_wave[nfm::WAVES];
+    __shared__ uint32_t s_wave[nfc::WAVES];
     const bool vertices = (int64_t)blockIdx.x < blocks_v;
     const int64_t block = vertices ? (int64_t)blockIdx.x : (int64_t)blockIdx.x - blocks_v;
-    const int64_t at = block * nfm::THREADS + threadIdx.x;
+    const int64_t at = block * nfc::THREADS + threadIdx.x;
     uint32_t keep = 0;
     if (at < (vertices ? n_vertices : n_faces)) {
         const int label = vertices ? vertex_label[at] : face_label[at];
         keep = label >= 0 && nf_mc_keeps(header, face_counts, label) ? 1u : 0u;
     }
-    uint32_t total;
-    nf_iso_block_scan<nfm::WAVES>(keep, s_wave, &total);
+    const uint32_t total = nf_block_total<nfc::WAVES>(keep, s_wave);
     if (threadIdx.x == 0) (vertices ? block_v : block_f)[block] = total;
 }
 
 // ---- compaction
-__global__ void __launch_bounds__(nfm::THREADS) k_mc_emit_verts(const float* __restrict__ vertices, const float* __restrict__ normals,
+__global__ void __launch_bounds__(nfc::THREADS) k_mc_emit_verts(const float* __restrict__ vertices, const float* __restrict__ normals,
                                                                 const int* __restrict__ vertex_label, const int* __restrict__ face_counts,
                                                                 int64_t n_vertices, const nfm::Header* __restrict__ header,
                                                                 const uint32_t* __restrict__ block_v, int* __restrict__ new_id,
                                                                 float* __restrict__ out_vertices, int64_t cap_vertices, float* __restrict__ out_normals) {
-    __shared__ uint32_t s_wave[nfm::WAVES];
-    const int64_t v = (int64_t)blockIdx.x * nfm::THREADS + threadIdx.x;
+    __shared__ uint32_t s_wave[nfc::WAVES];
+    const int64_t v = (int64_t)blockIdx.x * nfc::THREADS + threadIdx.x;
     const uint32_t keep = v < n_vertices && nf_mc_keeps(header, face_counts, vertex_label[v]) ? 1u : 0u;
     uint32_t total;
-    const int64_t id = (int64_t)block_v[blockIdx.x] + nf_iso_block_scan<nfm::WAVES>(keep, s_wave, &total) - keep;
+    const int64_t id = (int64_t)block_v[blockIdx.x] + nf_block_scan<nfc::WAVES>(keep, s_wave, &total) - keep;
     if (!keep) return;
     new_id[v] = (int)id;
     if (id >= cap_vertices) return;
@@ -314,22 +276,22 @@ __global__ void __launch_bounds__(nfm::THREADS) k_mc_emit_verts(const float* __r
     }
 }
 
-__global__ void __launch_bounds__(nfm::THREADS) k_mc_emit_faces(const int* __restrict__ faces, const int* __restrict__ face_label,
+__global__ void __launch_bounds__(nfc::THREADS) k_mc_emit_faces(const int* __restrict__ faces, const int* __restrict__ face_label,
                                                                 const int* __restrict__ face_counts, int64_t n_faces,
                                                                 int64_t n_vertices, const nfm::Header* __restrict__ header,
                                                                 const uint32_t* __restrict__ block_f, const int* __restrict__ new_id,
                                                                 int* __restrict__ out_faces, int64_t cap_faces) {
-    __shared__ uint32_t s_wave[nfm::WAVES];
-    const int64_t f = (int64_t)blockIdx.x * nfm::THREADS + threadIdx.x;
+    __shared__ uint32_t s_wave[nfc::WAVES];
+    const int64_t f = (int64_t)blockIdx.x * nfc::THREADS + threadIdx.x;
     uint32_t keep = 0;
     if (f < n_faces) {
         const int label = face_label[f];
         keep = label >= 0 && nf_mc_keeps(header, face_counts, label) ? 1u : 0u;
     }
     uint32_t total;
-    const int64_t row = (int64_t)block_f[blockIdx.x] + nf_iso_block_scan<nfm::WAVES>(keep, s_wave, &total) - keep;
+    const int64_t row = (int64_t)block_f[blockIdx.x] + nf_block_scan<nfc::WAVES>(keep, s_wave, &total) - keep;
     if (!keep || row >= cap_faces) return;
-    const NfMcFace t = nf_mc_face(faces, f, n_vertices);            // label >= 0 says valid, and its vertices are kept; checked all the same
+    const NfFace t = nf_face(faces, f, n_vertices);                 // label >= 0 says valid, and its vertices are kept; checked all the same
     out_faces[row * 3 + 0] = t.valid ? new_id[t.a] : -1;
     out_faces[row * 3 + 1] = t.valid ? new_id[t.b] : -1;
     out_faces[row * 3 + 2] = t.valid ? new_id[t.c] : -1;
@@ -345,14 +307,14 @@ extern "C" int nf_mesh_components_label(const int* faces, int64_t n_vertices, in
     char* ws = static_cast<char*>(workspace);
     int* parent = reinterpret_cast<int*>(ws + p.off_parent);
     uint32_t* block_v = reinterpret_cast<uint32_t*>(ws + p.off_block_v);
-    const dim3 threads(nfm::THREADS), grid_v((unsigned)p.blocks_v), grid_f((unsigned)p.blocks_f), grid_vf((unsigned)(p.blocks_v + p.blocks_f));
+    const dim3 threads(nfc::THREADS), grid_v((unsigned)p.blocks_v), grid_f((unsigned)p.blocks_f), grid_vf((unsigned)(p.blocks_v + p.blocks_f));
     hipStream_t s = nf_s(stream);
     if (n_vertices) {
         hipLaunchKernelGGL(k_mc_init, grid_v, threads, 0, s, parent, n_vertices);
         if (n_faces) hipLaunchKernelGGL(k_mc_hook, grid_f, threads, 0, s, faces, n_vertices, n_faces, parent);
         hipLaunchKernelGGL(k_mc_flatten, grid_v, threads, 0, s, parent, n_vertices, block_v);
     }
-    hipLaunchKernelGGL(k_mc_scan, dim3(1), dim3(nfm::SCAN_THREADS), 0, s, block_v, p.blocks_v, 0, block_v, (int64_t)0, 0, 1,
+    hipLaunchKernelGGL(k_mc_scan, dim3(1), dim3(nfc::SCAN_THREADS), 0, s, block_v, p.blocks_v, 0, block_v, (int64_t)0, 0, 1,
                        reinterpret_cast<long long*>(ws), reinterpret_cast<long long*>(counts_dev));
     if (n_vertices)
         hipLaunchKernelGGL(k_mc_rank, grid_v, threads, 0, s, parent, n_vertices, block_v, vertex_label, face_counts, vertex_counts);
@@ -374,12 +336,12 @@ extern "C" int nf_mesh_components_select(const int* vertex_label, const int* fac
     uint32_t* block_v = reinterpret_cast<uint32_t*>(ws + p.off_block_v);
     uint32_t* block_f = reinterpret_cast<uint32_t*>(ws + p.off_block_f);
     hipStream_t s = nf_s(stream);
-    hipLaunchKernelGGL(k_mc_select, dim3(1), dim3(nfm::SCAN_THREADS), 0, s, face_counts, largest ? 1 : 0, largest ? (long long)1 : (long long)min_faces,
+    hipLaunchKernelGGL(k_mc_select, dim3(1), dim3(nfc::SCAN_THREADS), 0, s, face_counts, largest ? 1 : 0, largest ? (long long)1 : (long long)min_faces,
                        header, reinterpret_cast<long long*>(counts_dev));
     if (n_vertices || n_faces)
-        hipLaunchKernelGGL(k_mc_keep, dim3((unsigned)(p.blocks_v + p.blocks_f)), dim3(nfm::THREADS), 0, s, vertex_label, face_label, face_counts, n_vertices,
+        hipLaunchKernelGGL(k_mc_keep, dim3((unsigned)(p.blocks_v + p.blocks_f)), dim3(nfc::THREADS), 0, s, vertex_label, face_label, face_counts, n_vertices,
                            n_faces, p.blocks_v, header, block_v, block_f);
-    hipLaunchKernelGGL(k_mc_scan, dim3(1), dim3(nfm::SCAN_THREADS), 0, s, block_v, p.blocks_v, 1, block_f, p.blocks_f, 2, 2,
+    hipLaunchKernelGGL(k_mc_scan, dim3(1), dim3(nfc::SCAN_THREADS), 0, s, block_v, p.blocks_v, 1, block_f, p.blocks_f, 2, 2,
                        reinterpret_cast<long long*>(ws), reinterpret_cast<long long*>(counts_dev));
     NF_RETURN_LAUNCH();
 }
@@ -398,11 +360,11 @@ extern "C" int nf_mesh_components_emit(const float* vertices, const int* faces, 
     int* new_id = reinterpret_cast<int*>(ws + p.off_new_id);
     hipStream_t s = nf_s(stream);
     if (n_vertices)
-        hipLaunchKernelGGL(k_mc_emit_verts, dim3((unsigned)p.blocks_v), dim3(nfm::THREADS), 0, s, vertices, out_normals ? normals : nullptr, vertex_label,
+        hipLaunchKernelGGL(k_mc_emit_verts, dim3((unsigned)p.blocks_v), dim3(nfc::THREADS), 0, s, vertices, out_normals ? normals : nullptr, vertex_label,
                            face_counts, n_vertices, header, reinterpret_cast<const uint32_t*>(ws + p.off_block_v), new_id, out_vertices, cap_vertices,
                            out_normals);
     if (n_faces)
-        hipLaunchKernelGGL(k_mc_emit_faces, dim3((unsigned)p.blocks_f), dim3(nfm::THREADS), 0, s, faces, face_label, face_counts, n_faces, n_vertices,
+        hipLaunchKernelGGL(k_mc_emit_faces, dim3((unsigned)p.blocks_f), dim3(nfc::THREADS), 0, s, faces, face_label, face_counts, n_faces, n_vertices,
                            header, reinterpret_cast<const uint32_t*>(ws + p.off_block_f), new_id, out_faces, cap_faces);
     NF_RETURN_LAUNCH();
 }

@@ -13,7 +13,7 @@
 // construction (template parameter ADJ: what a face emits, and whether equal entries of a row are merged and counted):
 //   k_ms_zero     cursor[0 .. V] = 0; the boundary count = 0
 //   k_ms_count    every valid face: cursor[row] += 1 per entry (integer atomicAdd: a sum)
-//   k_ms_sum / k_ms_scan1 / k_ms_offsets   exclusive scan -> raw_start[0 .. V]; cursor = raw_start
+//   k_ms_sum / k_ms_scan1 / k_ms_offsets   exclusive scan (the block sums: nf_scan_dev.h) -> raw_start[0 .. V]; cursor = raw_start
 //   k_ms_fill     every valid face: raw[cursor[row]++] = entry (integer atomicAdd; the order WITHIN a row is arbitrary here ...)
 //   k_ms_sort     ... and fixed here: a row of at most SHORT_ROW entries is sorted by its thread (insertion sort in an LDS column),
 //                 a longer one by its wave (rank sort, O(d^2 / 64), into a second buffer).  ADJ: equal entries merged, their number
@@ -25,15 +25,11 @@
 // thread or one wave from k_ms_sort on, so nothing after k_ms_fill depends on arrival order: two calls give the same bits.  The
 // workspace may arrive with any content: every word a kernel reads was written by an earlier kernel of the same call.
 #include <math.h>
-#include "nf_grid_dev.h"
+#include "nf_mesh_dev.h"
+#include "nf_scan_dev.h"
 
 namespace nfs {
-constexpr int THREADS = 256;               // vertices, faces or rows per workgroup (4 waves), one block sum each
-constexpr int WAVES = THREADS / NF_WAVE;
-constexpr int SCAN_THREADS = 1024;         // k_ms_scan1: its one workgroup
-constexpr int SCAN_WAVES = SCAN_THREADS / NF_WAVE;
 constexpr int SCAN_PER_THREAD = 4;         // k_ms_scan1: block sums per thread and round (a round takes 4096 sums: 2^20 rows)
-constexpr int HEADER = 256;                // bytes at the workspace's start: the two totals
 constexpr int SHORT_ROW = 32;              // entries (repeats included) of the longest row one thread sorts; longer rows take a wave
 }  // namespace nfs
 
@@ -43,23 +39,21 @@ struct NfMsPlan {
     size_t off_cursor, off_raw_start, off_block, off_a, off_b, off_c, bytes;
 };
 
-static inline size_t nf_ms_up(size_t b) { return (b + 255) / 256 * 256; }
-
 // false: a size the plan does not serve.  V and 6 F stay below 2^31 (ids, positions and counts are int32); either may be 0.
 static inline bool nf_ms_plan(int64_t n_vertices, int64_t n_faces, NfMsPlan* p) {
     if (n_vertices < 0 || n_faces < 0 || n_vertices > 0x7fffffff || n_faces > 0x7fffffff / 6) return false;
     p->rows = n_vertices + 1;
-    p->blocks_rows = (p->rows + nfs::THREADS - 1) / nfs::THREADS;
-    p->blocks_v = (n_vertices + nfs::THREADS - 1) / nfs::THREADS;
-    p->blocks_f = (n_faces + nfs::THREADS - 1) / nfs::THREADS;
-    size_t at = nfs::HEADER;
-    p->off_cursor = at, at += nf_ms_up((size_t)p->rows * 4);
-    p->off_raw_start = at, at += nf_ms_up((size_t)p->rows * 4);
-    p->off_block = at, at += nf_ms_up((size_t)p->blocks_rows * 4);
-    p->off_a = at, at += nf_ms_up((size_t)n_faces * 24);           // the unsorted rows; (ADJ) then the merged ones
-    p->off_b = at, at += nf_ms_up((size_t)n_faces * 24);           // (ADJ) the multiplicities; else the sorted rows
-    p->off_c = at, at += nf_ms_up((size_t)n_faces * 24);           // (ADJ) a long row, sorted, before it is merged; else the face vectors
-    p->bytes = at;
+    p->blocks_rows = nf_blocks(p->rows);
+    p->blocks_v = nf_blocks(n_vertices);
+    p->blocks_f = nf_blocks(n_faces);
+    NfWorkspace ws;
+    p->off_cursor = ws.take((size_t)p->rows * 4);
+    p->off_raw_start = ws.take((size_t)p->rows * 4);
+    p->off_block = ws.take((size_t)p->blocks_rows * 4);
+    p->off_a = ws.take((size_t)n_faces * 24);                       // the unsorted rows; (ADJ) then the merged ones
+    p->off_b = ws.take((size_t)n_faces * 24);                       // (ADJ) the multiplicities; else the sorted rows
+    p->off_c = ws.take((size_t)n_faces * 24);                       // (ADJ) a long row, sorted, before it is merged; else the face vectors
+    p->bytes = ws.at;
     return true;
 }
 
@@ -68,20 +62,10 @@ extern "C" size_t nf_mesh_smooth_workspace_bytes(int64_t n_vertices, int64_t n_f
     return nf_ms_plan(n_vertices, n_faces, &p) ? p.bytes : 0;
 }
 
-// the three indices of face f (64-bit addressing) and whether all lie in [0, V)
-struct NfMsFace { int a, b, c; bool valid; };
-
-__device__ __forceinline__ NfMsFace nf_ms_face(const int* __restrict__ faces, int64_t f, int64_t n_vertices) {
-    NfMsFace t;
-    t.a = faces[f * 3 + 0], t.b = faces[f * 3 + 1], t.c = faces[f * 3 + 2];
-    t.valid = t.a >= 0 && t.a < n_vertices && t.b >= 0 && t.b < n_vertices && t.c >= 0 && t.c < n_vertices;
-    return t;
-}
-
 // what a valid face puts into the table: ADJ, (v, w) and (w, v) per side with distinct ends -- at most 6; else (v, f) for each of
 // its distinct vertices -- at most 3
 template <bool ADJ, class Emit>
-__device__ __forceinline__ void nf_ms_entries(const NfMsFace& t, int f, Emit emit) {
+__device__ __forceinline__ void nf_ms_entries(const NfFace& t, int f, Emit emit) {
     if (ADJ) {
         if (t.a != t.b) emit(t.a, t.b), emit(t.b, t.a);
         if (t.b != t.c) emit(t.b, t.c), emit(t.c, t.b);
@@ -94,62 +78,44 @@ __device__ __forceinline__ void nf_ms_entries(const NfMsFace& t, int f, Emit emi
 }
 
 // ---- the table builder
-__global__ void __launch_bounds__(nfs::THREADS) k_ms_zero(int* __restrict__ cursor, int64_t rows, unsigned long long* __restrict__ counts) {
-    const int64_t i = (int64_t)blockIdx.x * nfs::THREADS + threadIdx.x;
+__global__ void __launch_bounds__(nfc::THREADS) k_ms_zero(int* __restrict__ cursor, int64_t rows, unsigned long long* __restrict__ counts) {
+    const int64_t i = (int64_t)blockIdx.x * nfc::THREADS + threadIdx.x;
     if (i < rows) cursor[i] = 0;
     if (i == 0 && counts) counts[1] = 0ull;
 }
 
 template <bool ADJ>
-__global__ void __launch_bounds__(nfs::THREADS) k_ms_count(const int* __restrict__ faces, int64_t n_vertices, int64_t n_faces, int* __restrict__ cursor) {
-    const int64_t f = (int64_t)blockIdx.x * nfs::THREADS + threadIdx.x;
+__global__ void __launch_bounds__(nfc::THREADS) k_ms_count(const int* __restrict__ faces, int64_t n_vertices, int64_t n_faces, int* __restrict__ cursor) {
+    const int64_t f = (int64_t)blockIdx.x * nfc::THREADS + threadIdx.x;
     if (f >= n_faces) return;
-    const NfMsFace t = nf_ms_face(faces, f, n_vertices);            // range-checked before anything is indexed
+    const NfFace t = nf_face(faces, f, n_vertices);                 // range-checked before anything is indexed
     if (!t.valid) return;
     nf_ms_entries<ADJ>(t, (int)f, [&](int row, int) { atomicAdd(cursor + row, 1); });
 }
 
 template <bool ADJ>
-__global__ void __launch_bounds__(nfs::THREADS) k_ms_fill(const int* __restrict__ faces, int64_t n_vertices, int64_t n_faces, int* __restrict__ cursor,
+__global__ void __launch_bounds__(nfc::THREADS) k_ms_fill(const int* __restrict__ faces, int64_t n_vertices, int64_t n_faces, int* __restrict__ cursor,
                                                           int* __restrict__ raw) {
-    const int64_t f = (int64_t)blockIdx.x * nfs::THREADS + threadIdx.x;
+    const int64_t f = (int64_t)blockIdx.x * nfc::THREADS + threadIdx.x;
     if (f >= n_faces) return;
-    const NfMsFace t = nf_ms_face(faces, f, n_vertices);
+    const NfFace t = nf_face(faces, f, n_vertices);
     if (!t.valid) return;
     nf_ms_entries<ADJ>(t, (int)f, [&](int row, int entry) { raw[atomicAdd(cursor + row, 1)] = entry; });   // the same faces as k_ms_count: inside the row
 }
 
 // the scan of x[0 .. n_valid) (entry n_valid .. rows-1 counts 0) in three kernels: the sum of every workgroup's 256 entries ...
-__global__ void __launch_bounds__(nfs::THREADS) k_ms_sum(const int* x, int64_t n_valid, uint32_t* __restrict__ block) {
-    __shared__ uint32_t s_wave[nfs::WAVES];
-    const int64_t i = (int64_t)blockIdx.x * nfs::THREADS + threadIdx.x;
-    uint32_t total;
-    nf_iso_block_scan<nfs::WAVES>(i < n_valid ? (uint32_t)x[i] : 0u, s_wave, &total);
+__global__ void __launch_bounds__(nfc::THREADS) k_ms_sum(const int* x, int64_t n_valid, uint32_t* __restrict__ block) {
+    __shared__ uint32_t s_wave[nfc::WAVES];
+    const int64_t i = (int64_t)blockIdx.x * nfc::THREADS + threadIdx.x;
+    const uint32_t total = nf_block_total<nfc::WAVES>(i < n_valid ? (uint32_t)x[i] : 0u, s_wave);
     if (threadIdx.x == 0) block[blockIdx.x] = total;
 }
 
 // ... one workgroup: the block sums -> their exclusive prefixes in place; the total to *total_out ...
-__global__ void __launch_bounds__(nfs::SCAN_THREADS) k_ms_scan1(uint32_t* __restrict__ a, int64_t n_blocks, long long* __restrict__ header_slot,
+__global__ void __launch_bounds__(nfc::SCAN_THREADS) k_ms_scan1(uint32_t* __restrict__ a, int64_t n_blocks, long long* __restrict__ header_slot,
                                                                long long* __restrict__ total_out) {
-    __shared__ uint32_t s_wave[nfs::SCAN_WAVES];
-    uint32_t carry = 0;
-    for (int64_t base = 0; base < n_blocks; base += (int64_t)nfs::SCAN_THREADS * nfs::SCAN_PER_THREAD) {
-        const int64_t at = base + (int64_t)threadIdx.x * nfs::SCAN_PER_THREAD;
-        uint32_t v[nfs::SCAN_PER_THREAD], sum = 0;
-#pragma unroll
-        for (int q = 0; q < nfs::SCAN_PER_THREAD; ++q) {
-            v[q] = at + q < n_blocks ? a[at + q] : 0u;
-            sum += v[q];
-        }
-        uint32_t total;
-        uint32_t run = carry + nf_iso_block_scan<nfs::SCAN_WAVES>(sum, s_wave, &total) - sum;
-#pragma unroll
-        for (int q = 0; q < nfs::SCAN_PER_THREAD; ++q) {
-            if (at + q < n_blocks) a[at + q] = run;
-            run += v[q];
-        }
-        carry += total;
-    }
+    __shared__ uint32_t s_wave[nfc::SCAN_WAVES];
+    const uint32_t carry = nf_scan_block_sums<nfs::SCAN_PER_THREAD>(a, n_blocks, s_wave);
     if (threadIdx.x == 0) {
         *header_slot = (long long)carry;
         if (total_out) *total_out = (long long)carry;
@@ -158,13 +124,13 @@ __global__ void __launch_bounds__(nfs::SCAN_THREADS) k_ms_scan1(uint32_t* __rest
 
 // ... and out[i] = the sum of x[0 .. i) for i in [0, rows) (out2 too, unless NULL).  x may be out or out2: a thread reads its own
 // entry before the workgroup's scan and writes it after.
-__global__ void __launch_bounds__(nfs::THREADS) k_ms_offsets(const int* x, int64_t n_valid, int64_t rows, const uint32_t* __restrict__ block, int* out,
+__global__ void __launch_bounds__(nfc::THREADS) k_ms_offsets(const int* x, int64_t n_valid, int64_t rows, const uint32_t* __restrict__ block, int* out,
                                                              int* out2) {
-    __shared__ uint32_t s_wave[nfs::WAVES];
-    const int64_t i = (int64_t)blockIdx.x * nfs::THREADS + threadIdx.x;
+    __shared__ uint32_t s_wave[nfc::WAVES];
+    const int64_t i = (int64_t)blockIdx.x * nfc::THREADS + threadIdx.x;
     const uint32_t mine = i < n_valid ? (uint32_t)x[i] : 0u;
     uint32_t total;
-    const uint32_t before = block[blockIdx.x] + nf_iso_block_scan<nfs::WAVES>(mine, s_wave, &total) - mine;
+    const uint32_t before = block[blockIdx.x] + nf_block_scan<nfc::WAVES>(mine, s_wave, &total) - mine;
     if (i >= rows) return;
     out[i] = (int)before;
     if (out2) out2[i] = (int)before;
@@ -174,10 +140,10 @@ __global__ void __launch_bounds__(nfs::THREADS) k_ms_offsets(const int* x, int64
 // times each was there to `out`, the number of distinct entries to length[v]; `sorted` holds a long row between its two steps.
 // Otherwise the row, ascending, to `out` (sorted is not used).  No lane leaves early: the long rows are the whole wave's work.
 template <bool MERGE>
-__global__ void __launch_bounds__(nfs::THREADS) k_ms_sort(const int* __restrict__ raw_start, int64_t n_vertices, int* raw, int* sorted_buf, int* out,
+__global__ void __launch_bounds__(nfc::THREADS) k_ms_sort(const int* __restrict__ raw_start, int64_t n_vertices, int* raw, int* sorted_buf, int* out,
                                                           int* __restrict__ length) {
-    __shared__ int s_row[nfs::SHORT_ROW * nfs::THREADS];            // entry i of thread t at [i * THREADS + t]: no bank conflicts
-    const int64_t v = (int64_t)blockIdx.x * nfs::THREADS + threadIdx.x;
+    __shared__ int s_row[nfs::SHORT_ROW * nfc::THREADS];            // entry i of thread t at [i * THREADS + t]: no bank conflicts
+    const int64_t v = (int64_t)blockIdx.x * nfc::THREADS + threadIdx.x;
     const int lane = threadIdx.x & 63;
     int begin = 0, d = 0;
     if (v < n_vertices) {
@@ -186,26 +152,26 @@ __global__ void __launch_bounds__(nfs::THREADS) k_ms_sort(const int* __restrict_
     }
     if (d <= nfs::SHORT_ROW) {
         int* r = s_row + threadIdx.x;
-        for (int i = 0; i < d; ++i) r[i * nfs::THREADS] = raw[(int64_t)begin + i];
+        for (int i = 0; i < d; ++i) r[i * nfc::THREADS] = raw[(int64_t)begin + i];
         for (int i = 1; i < d; ++i) {
-            const int x = r[i * nfs::THREADS];
+            const int x = r[i * nfc::THREADS];
             int j = i;
-            for (; j > 0 && r[(j - 1) * nfs::THREADS] > x; --j) r[j * nfs::THREADS] = r[(j - 1) * nfs::THREADS];
-            r[j * nfs::THREADS] = x;
+            for (; j > 0 && r[(j - 1) * nfc::THREADS] > x; --j) r[j * nfc::THREADS] = r[(j - 1) * nfc::THREADS];
+            r[j * nfc::THREADS] = x;
         }
         if (MERGE) {
             int u = 0;
             for (int i = 0; i < d;) {
-                const int x = r[i * nfs::THREADS];
+                const int x = r[i * nfc::THREADS];
                 int run = 1;
-                while (i + run < d && r[(i + run) * nfs::THREADS] == x) ++run;
+                while (i + run < d && r[(i + run) * nfc::THREADS] == x) ++run;
                 raw[(int64_t)begin + u] = x;
                 out[(int64_t)begin + u] = run;
                 ++u, i += run;
             }
             if (v < n_vertices) length[v] = u;
         } else {
-            for (int i = 0; i < d; ++i) out[(int64_t)begin + i] = r[i * nfs::THREADS];
+            for (int i = 0; i < d; ++i) out[(int64_t)begin + i] = r[i * nfc::THREADS];
         }
     }
     unsigned long long todo = __ballot(d > nfs::SHORT_ROW);
@@ -260,12 +226,12 @@ __global__ void __launch_bounds__(nfs::THREADS) k_ms_sort(const int* __restrict_
 }
 
 // rows to their final place (E <= 6 F entries, and none past E is written); boundary[v] = some edge of v has multiplicity 1
-__global__ void __launch_bounds__(nfs::THREADS) k_ms_compact(const int* __restrict__ raw_start, const int* __restrict__ merged, const int* __restrict__ times,
+__global__ void __launch_bounds__(nfc::THREADS) k_ms_compact(const int* __restrict__ raw_start, const int* __restrict__ merged, const int* __restrict__ times,
                                                              const int* __restrict__ row_start, int64_t n_vertices, int* __restrict__ neighbours,
                                                              int* __restrict__ multiplicity, uint8_t* __restrict__ boundary,
                                                              unsigned long long* __restrict__ counts) {
-    __shared__ uint32_t s_wave[nfs::WAVES];
-    const int64_t v = (int64_t)blockIdx.x * nfs::THREADS + threadIdx.x;
+    __shared__ uint32_t s_wave[nfc::WAVES];
+    const int64_t v = (int64_t)blockIdx.x * nfc::THREADS + threadIdx.x;
     uint32_t open = 0;
     if (v < n_vertices) {
         const int64_t from = raw_start[v], to = row_start[v];
@@ -278,16 +244,15 @@ __global__ void __launch_bounds__(nfs::THREADS) k_ms_compact(const int* __restri
         }
         boundary[v] = (uint8_t)open;
     }
-    uint32_t total;
-    nf_iso_block_scan<nfs::WAVES>(open, s_wave, &total);
+    const uint32_t total = nf_block_total<nfc::WAVES>(open, s_wave);
     if (threadIdx.x == 0 && total) atomicAdd(counts + 1, (unsigned long long)total);
 }
 
 // ---- the pass.  row_start == NULL: a copy
-__global__ void __launch_bounds__(nfs::THREADS) k_ms_pass(const float* __restrict__ src, int64_t n_vertices, const int* __restrict__ row_start,
+__global__ void __launch_bounds__(nfc::THREADS) k_ms_pass(const float* __restrict__ src, int64_t n_vertices, const int* __restrict__ row_start,
                                                           const int* __restrict__ neighbours, const uint8_t* __restrict__ pinned, float factor,
                                                           float* __restrict__ dst) {
-    const int64_t v = (int64_t)blockIdx.x * nfs::THREADS + threadIdx.x;
+    const int64_t v = (int64_t)blockIdx.x * nfc::THREADS + threadIdx.x;
     if (v >= n_vertices) return;
     const float px = src[v * 3 + 0], py = src[v * 3 + 1], pz = src[v * 3 + 2];
     float ox = px, oy = py, oz = pz;
@@ -313,11 +278,11 @@ __global__ void __launch_bounds__(nfs::THREADS) k_ms_pass(const float* __restric
 }
 
 // ---- normals
-__global__ void __launch_bounds__(nfs::THREADS) k_ms_face_cross(const float* __restrict__ vertices, const int* __restrict__ faces, int64_t n_vertices,
+__global__ void __launch_bounds__(nfc::THREADS) k_ms_face_cross(const float* __restrict__ vertices, const int* __restrict__ faces, int64_t n_vertices,
                                                                 int64_t n_faces, float* __restrict__ cross) {
-    const int64_t f = (int64_t)blockIdx.x * nfs::THREADS + threadIdx.x;
+    const int64_t f = (int64_t)blockIdx.x * nfc::THREADS + threadIdx.x;
     if (f >= n_faces) return;
-    const NfMsFace t = nf_ms_face(faces, f, n_vertices);
+    const NfFace t = nf_face(faces, f, n_vertices);
     if (!t.valid) return;                                           // no row lists an invalid face
     const float* a = vertices + (int64_t)t.a * 3;
     const float* b = vertices + (int64_t)t.b * 3;
@@ -329,9 +294,9 @@ __global__ void __launch_bounds__(nfs::THREADS) k_ms_face_cross(const float* __r
     cross[f * 3 + 2] = nf_sub(nf_mul(ux, wy), nf_mul(uy, wx));
 }
 
-__global__ void __launch_bounds__(nfs::THREADS) k_ms_vertex_normals(const int* __restrict__ raw_start, const int* __restrict__ incident,
+__global__ void __launch_bounds__(nfc::THREADS) k_ms_vertex_normals(const int* __restrict__ raw_start, const int* __restrict__ incident,
                                                                     const float* __restrict__ cross, int64_t n_vertices, float* __restrict__ normals) {
-    const int64_t v = (int64_t)blockIdx.x * nfs::THREADS + threadIdx.x;
+    const int64_t v = (int64_t)blockIdx.x * nfc::THREADS + threadIdx.x;
     if (v >= n_vertices) return;
     const int64_t b = raw_start[v], e = raw_start[v + 1];
     float sx = 0.f, sy = 0.f, sz = 0.f;
@@ -364,12 +329,12 @@ static inline void nf_ms_build(const NfMsPlan& p, const int* faces, int64_t n_ve
     int* b = reinterpret_cast<int*>(ws + p.off_b);
     int* c = reinterpret_cast<int*>(ws + p.off_c);
     long long* header = reinterpret_cast<long long*>(ws);
-    const dim3 threads(nfs::THREADS), grid_rows((unsigned)p.blocks_rows), grid_v((unsigned)p.blocks_v), grid_f((unsigned)p.blocks_f);
+    const dim3 threads(nfc::THREADS), grid_rows((unsigned)p.blocks_rows), grid_v((unsigned)p.blocks_v), grid_f((unsigned)p.blocks_f);
     const bool any = n_vertices && n_faces;
     hipLaunchKernelGGL(k_ms_zero, grid_rows, threads, 0, s, cursor, p.rows, counts);
     if (any) hipLaunchKernelGGL(k_ms_count<ADJ>, grid_f, threads, 0, s, faces, n_vertices, n_faces, cursor);
     hipLaunchKernelGGL(k_ms_sum, grid_rows, threads, 0, s, cursor, n_vertices, block);
-    hipLaunchKernelGGL(k_ms_scan1, dim3(1), dim3(nfs::SCAN_THREADS), 0, s, block, p.blocks_rows, header, (long long*)nullptr);
+    hipLaunchKernelGGL(k_ms_scan1, dim3(1), dim3(nfc::SCAN_THREADS), 0, s, block, p.blocks_rows, header, (long long*)nullptr);
     hipLaunchKernelGGL(k_ms_offsets, grid_rows, threads, 0, s, cursor, n_vertices, p.rows, block, raw_start, cursor);
     if (any) hipLaunchKernelGGL(k_ms_fill<ADJ>, grid_f, threads, 0, s, faces, n_vertices, n_faces, cursor, a);
     if (n_vertices) hipLaunchKernelGGL(k_ms_sort<ADJ>, grid_v, threads, 0, s, raw_start, n_vertices, a, c, b, length);
@@ -384,11 +349,11 @@ extern "C" int nf_mesh_smooth_adjacency(const int* faces, int64_t n_vertices, in
     char* ws = static_cast<char*>(workspace);
     uint32_t* block = reinterpret_cast<uint32_t*>(ws + p.off_block);
     unsigned long long* counts = reinterpret_cast<unsigned long long*>(counts_dev);
-    const dim3 threads(nfs::THREADS), grid_rows((unsigned)p.blocks_rows), grid_v((unsigned)p.blocks_v);
+    const dim3 threads(nfc::THREADS), grid_rows((unsigned)p.blocks_rows), grid_v((unsigned)p.blocks_v);
     hipStream_t s = nf_s(stream);
     nf_ms_build<true>(p, faces, n_vertices, n_faces, ws, row_start, counts, s);
     hipLaunchKernelGGL(k_ms_sum, grid_rows, threads, 0, s, row_start, n_vertices, block);
-    hipLaunchKernelGGL(k_ms_scan1, dim3(1), dim3(nfs::SCAN_THREADS), 0, s, block, p.blocks_rows, reinterpret_cast<long long*>(ws) + 1,
+    hipLaunchKernelGGL(k_ms_scan1, dim3(1), dim3(nfc::SCAN_THREADS), 0, s, block, p.blocks_rows, reinterpret_cast<long long*>(ws) + 1,
                        reinterpret_cast<long long*>(counts_dev));
     hipLaunchKernelGGL(k_ms_offsets, grid_rows, threads, 0, s, row_start, n_vertices, p.rows, block, row_start, (int*)nullptr);
     if (n_vertices)
@@ -406,7 +371,7 @@ extern "C" int nf_mesh_smooth_run(const float* vertices, int64_t n_vertices, con
     if (n_vertices && passes && (!row_start || !neighbours)) return NF_EINVAL;
     if (n_vertices && passes > 1 && (!tmp || tmp == out || tmp == vertices)) return NF_EINVAL;
     if (!n_vertices) return 0;
-    const dim3 threads(nfs::THREADS), grid((unsigned)((n_vertices + nfs::THREADS - 1) / nfs::THREADS));
+    const dim3 threads(nfc::THREADS), grid((unsigned)nf_blocks(n_vertices));
     hipStream_t s = nf_s(stream);
     if (!passes) hipLaunchKernelGGL(k_ms_pass, grid, threads, 0, s, vertices, n_vertices, (const int*)nullptr, (const int*)nullptr, (const uint8_t*)nullptr, 0.f, out);
     const float* src = vertices;
@@ -430,8 +395,8 @@ extern "C" int nf_mesh_smooth_normals(const float* vertices, const int* faces, i
     hipStream_t s = nf_s(stream);
     nf_ms_build<false>(p, faces, n_vertices, n_faces, ws, (int*)nullptr, (unsigned long long*)nullptr, s);
     if (n_faces)
-        hipLaunchKernelGGL(k_ms_face_cross, dim3((unsigned)p.blocks_f), dim3(nfs::THREADS), 0, s, vertices, faces, n_vertices, n_faces, cross);
-    hipLaunchKernelGGL(k_ms_vertex_normals, dim3((unsigned)p.blocks_v), dim3(nfs::THREADS), 0, s, reinterpret_cast<const int*>(ws + p.off_raw_start),
+        hipLaunchKernelGGL(k_ms_face_cross, dim3((unsigned)p.blocks_f), dim3(nfc::THREADS), 0, s, vertices, faces, n_vertices, n_faces, cross);
+    hipLaunchKernelGGL(k_ms_vertex_normals, dim3((unsigned)p.blocks_v), dim3(nfc::THREADS), 0, s, reinterpret_cast<const int*>(ws + p.off_raw_start),
                        reinterpret_cast<const int*>(ws + p.off_b), cross, n_vertices, normals);
     NF_RETURN_LAUNCH();
 }

@@ -15,7 +15,7 @@
 //   nf_sparse_grid_classify: k_sg_classify  one thread per brick: 8 corner values of the grid -> seed flag and side (1 B each)
 //                            k_sg_dilate    one thread per brick: any seed in the (2 dilate + 1)^3 neighbourhood -> active flag
 //   nf_sparse_grid_mark:     k_sg_count     one thread per point: to evaluate and not on the lattice? -> per-workgroup sums
-//                            k_sg_scan      one workgroup: exclusive scan of the sums in place; the total
+//                            k_sg_scan      one workgroup: the sums -> exclusive prefixes (nf_scan_dev.h); the total
 //   nf_sparse_grid_emit:     k_sg_emit      the same decision -> wave64 / workgroup scan -> slot in ascending linear index: index and
 //                                           coordinates; +-inf into the points that are not evaluated
 //   nf_sparse_grid_scatter:  k_sg_scatter   grid[index[t]] = values[t]
@@ -24,14 +24,10 @@
 // cache): k_sg_emit writes 4 B per point that is skipped and 16 B per point that is listed.
 #include "nf_grid_dev.h"
 
-namespace nfs {
-constexpr int THREADS = 256;
-constexpr int WAVES = THREADS / NF_WAVE;
-constexpr int SCAN_THREADS = 1024;         // k_sg_scan: its one workgroup
-constexpr int SCAN_WAVES = SCAN_THREADS / NF_WAVE;
-constexpr int SCAN_PER_THREAD = 16;        // k_sg_scan: block sums per thread and round
-constexpr int HEADER = 256;                // bytes: seed bricks, active bricks, points to evaluate beside the lattice, as int64
-}  // namespace nfs
+namespace nfg {
+constexpr int SCAN_PER_THREAD = 16;        // k_sg_scan: block sums per thread and round.  The header: seed bricks, active bricks, points
+                                           // to evaluate beside the lattice
+}  // namespace nfg
 
 // ---- plan
 struct NfSgDims {
@@ -44,21 +40,10 @@ struct NfSgPlan {
     size_t off_seed, off_side, off_active, off_block, bytes;
 };
 
-static inline size_t nf_sg_up(size_t b) { return (b + 255) / 256 * 256; }
-
-// the grids ops.isosurface serves: every axis >= 2, 7 * points and 12 * cells below 2^31
-static inline bool nf_sg_grid(int nx, int ny, int nz, int64_t* n_points) {
-    if (nx < 2 || ny < 2 || nz < 2) return false;
-    if ((int64_t)nx * ny > 0x7fffffff) return false;
-    const int64_t n = (int64_t)nx * ny * nz;
-    const int64_t cells = (int64_t)(nx - 1) * (ny - 1) * (nz - 1);
-    if (7 * n > 0x7fffffff || 12 * cells > 0x7fffffff) return false;
-    *n_points = n;
-    return true;
-}
-
+// false: a brick below 2 cells, or a grid ops.isosurface does not serve (nf_grid_points)
 static inline bool nf_sg_plan(int nx, int ny, int nz, int brick, NfSgPlan* p) {
-    if (brick < 2 || !nf_sg_grid(nx, ny, nz, &p->n_points)) return false;
+    p->n_points = nf_grid_points(nx, ny, nz);
+    if (brick < 2 || !p->n_points) return false;
     const int n[3] = {nx, ny, nz};
     const int longest = (nx > ny ? (nx > nz ? nx : nz) : (ny > nz ? ny : nz)) - 1;
     p->d.B = brick < longest ? brick : longest;                 // a larger brick is one brick per axis either way; B * (m + 1) < 2^29
@@ -69,13 +54,13 @@ static inline bool nf_sg_plan(int nx, int ny, int nz, int brick, NfSgPlan* p) {
         p->n_bricks *= p->d.m[a];
         p->n_lattice *= p->d.m[a] + 1;
     }
-    p->n_blocks = (p->n_points + nfs::THREADS - 1) / nfs::THREADS;
-    size_t at = nfs::HEADER;
-    p->off_seed = at, at += nf_sg_up((size_t)p->n_bricks);
-    p->off_side = at, at += nf_sg_up((size_t)p->n_bricks);
-    p->off_active = at, at += nf_sg_up((size_t)p->n_bricks);
-    p->off_block = at, at += nf_sg_up((size_t)p->n_blocks * 4);
-    p->bytes = at;
+    p->n_blocks = nf_blocks(p->n_points);
+    NfWorkspace ws;
+    p->off_seed = ws.take((size_t)p->n_bricks);
+    p->off_side = ws.take((size_t)p->n_bricks);
+    p->off_active = ws.take((size_t)p->n_bricks);
+    p->off_block = ws.take((size_t)p->n_blocks * 4);
+    p->bytes = ws.at;
     return true;
 }
 
@@ -84,22 +69,7 @@ extern "C" size_t nf_sparse_grid_workspace_bytes(int nx, int ny, int nz, int bri
     return nf_sg_plan(nx, ny, nz, brick, &p) ? p.bytes : 0;
 }
 
-struct NfSgBox { float lo[3], h[3]; };
-
-// false: !(lo < hi) on an axis (NaN bounds too).  h as nerf.mesh.grid_axes computes it: (hi - lo) / float32(n - 1), in float32.
-static inline bool nf_sg_box(const float* lo, const float* hi, const NfSgDims& d, NfSgBox* box) {
-    for (int a = 0; a < 3; ++a) {
-        if (!(lo[a] < hi[a])) return false;
-        box->lo[a] = lo[a];
-        box->h[a] = (hi[a] - lo[a]) / (float)(d.n[a] - 1);
-    }
-    return true;
-}
-
-// ---- device helpers
-// the coordinate of index i: multiply, then add, no fused multiply-add -- the bits of grid_axes
-__device__ __forceinline__ float nf_sg_coord(float lo, float h, int i) { return nf_add(lo, nf_mul((float)i, h)); }
-
+// ---- device helpers (the box and nf_grid_coord: nf_grid_dev.h)
 // first point index of brick b along an axis of n points (b == m: the last index)
 __device__ __forceinline__ int nf_sg_corner(int b, int B, int n) { return min(b * B, n - 1); }
 
@@ -130,30 +100,29 @@ __device__ __forceinline__ int nf_sg_decide(const NfIsoPoint g, const NfSgDims d
 }
 
 // ---- kernels
-__global__ void __launch_bounds__(nfs::THREADS) k_sg_lattice(NfSgDims d, NfSgBox box, int64_t n_lattice, int* __restrict__ index_out,
+__global__ void __launch_bounds__(nfc::THREADS) k_sg_lattice(NfSgDims d, NfGridBox box, int64_t n_lattice, int* __restrict__ index_out,
                                                              float* __restrict__ coords_out) {
-    const int64_t t = (int64_t)blockIdx.x * nfs::THREADS + threadIdx.x;
+    const int64_t t = (int64_t)blockIdx.x * nfc::THREADS + threadIdx.x;
     if (t >= n_lattice) return;
     const NfIsoPoint c = nf_iso_point(t, d.m[0] + 1, d.m[1] + 1);
     const int i = nf_sg_corner(c.i, d.B, d.n[0]), j = nf_sg_corner(c.j, d.B, d.n[1]), k = nf_sg_corner(c.k, d.B, d.n[2]);
     index_out[t] = (int)(((int64_t)k * d.n[1] + j) * d.n[0] + i);
-    coords_out[t * 3 + 0] = nf_sg_coord(box.lo[0], box.h[0], i);
-    coords_out[t * 3 + 1] = nf_sg_coord(box.lo[1], box.h[1], j);
-    coords_out[t * 3 + 2] = nf_sg_coord(box.lo[2], box.h[2], k);
+    coords_out[t * 3 + 0] = nf_grid_coord(box.lo[0], box.h[0], i);
+    coords_out[t * 3 + 1] = nf_grid_coord(box.lo[1], box.h[1], j);
+    coords_out[t * 3 + 2] = nf_grid_coord(box.lo[2], box.h[2], k);
 }
 
 // the workgroup's number of set flags -> one integer add
 __device__ __forceinline__ void nf_sg_count_flags(uint32_t flag, uint32_t* s_wave, unsigned long long* counter) {
-    uint32_t total;
-    nf_iso_block_scan<nfs::WAVES>(flag, s_wave, &total);
+    const uint32_t total = nf_block_total<nfc::WAVES>(flag, s_wave);
     if (threadIdx.x == 0 && total) atomicAdd(counter, (unsigned long long)total);
 }
 
-__global__ void __launch_bounds__(nfs::THREADS) k_sg_classify(const float* __restrict__ grid, NfSgDims d, float above, float below, int64_t n_bricks,
+__global__ void __launch_bounds__(nfc::THREADS) k_sg_classify(const float* __restrict__ grid, NfSgDims d, float above, float below, int64_t n_bricks,
                                                               uint8_t* __restrict__ seed_out, uint8_t* __restrict__ side_out,
                                                               unsigned long long* __restrict__ header) {
-    __shared__ uint32_t s_wave[nfs::WAVES];
-    const int64_t q = (int64_t)blockIdx.x * nfs::THREADS + threadIdx.x;
+    __shared__ uint32_t s_wave[nfc::WAVES];
+    const int64_t q = (int64_t)blockIdx.x * nfc::THREADS + threadIdx.x;
     uint32_t seed = 0;
     if (q < n_bricks) {
         const NfIsoPoint b = nf_iso_point(q, d.m[0], d.m[1]);
@@ -174,10 +143,10 @@ __global__ void __launch_bounds__(nfs::THREADS) k_sg_classify(const float* __res
     nf_sg_count_flags(seed, s_wave, header + 0);
 }
 
-__global__ void __launch_bounds__(nfs::THREADS) k_sg_dilate(const uint8_t* __restrict__ seed, NfSgDims d, int dilate, int64_t n_bricks,
+__global__ void __launch_bounds__(nfc::THREADS) k_sg_dilate(const uint8_t* __restrict__ seed, NfSgDims d, int dilate, int64_t n_bricks,
                                                             uint8_t* __restrict__ active_out, unsigned long long* __restrict__ header) {
-    __shared__ uint32_t s_wave[nfs::WAVES];
-    const int64_t q = (int64_t)blockIdx.x * nfs::THREADS + threadIdx.x;
+    __shared__ uint32_t s_wave[nfc::WAVES];
+    const int64_t q = (int64_t)blockIdx.x * nfc::THREADS + threadIdx.x;
     uint32_t active = 0;
     if (q < n_bricks) {
         const NfIsoPoint b = nf_iso_point(q, d.m[0], d.m[1]);
@@ -192,38 +161,20 @@ __global__ void __launch_bounds__(nfs::THREADS) k_sg_dilate(const uint8_t* __res
     nf_sg_count_flags(active, s_wave, header + 1);
 }
 
-__global__ void __launch_bounds__(nfs::THREADS) k_sg_count(NfSgDims d, int64_t n_points, const uint8_t* __restrict__ active,
+__global__ void __launch_bounds__(nfc::THREADS) k_sg_count(NfSgDims d, int64_t n_points, const uint8_t* __restrict__ active,
                                                            const uint8_t* __restrict__ side, uint32_t* __restrict__ block_sum) {
-    __shared__ uint32_t s_wave[nfs::WAVES];
-    const int64_t p = (int64_t)blockIdx.x * nfs::THREADS + threadIdx.x;
+    __shared__ uint32_t s_wave[nfc::WAVES];
+    const int64_t p = (int64_t)blockIdx.x * nfc::THREADS + threadIdx.x;
     const uint32_t flag = p < n_points && nf_sg_decide(nf_iso_point(p, d.n[0], d.n[1]), d, active, side) == NF_SG_EVAL ? 1u : 0u;
-    uint32_t total;
-    nf_iso_block_scan<nfs::WAVES>(flag, s_wave, &total);
+    const uint32_t total = nf_block_total<nfc::WAVES>(flag, s_wave);
     if (threadIdx.x == 0) block_sum[blockIdx.x] = total;
 }
 
 // one workgroup: the block sums -> exclusive prefixes in place; the total to the header; the header's three counts to counts_out
-__global__ void __launch_bounds__(nfs::SCAN_THREADS) k_sg_scan(uint32_t* __restrict__ a, int64_t n_blocks, long long* __restrict__ header,
+__global__ void __launch_bounds__(nfc::SCAN_THREADS) k_sg_scan(uint32_t* __restrict__ a, int64_t n_blocks, long long* __restrict__ header,
                                                                long long* __restrict__ counts_out) {
-    __shared__ uint32_t s_wave[nfs::SCAN_WAVES];
-    uint32_t carry = 0;
-    for (int64_t base = 0; base < n_blocks; base += (int64_t)nfs::SCAN_THREADS * nfs::SCAN_PER_THREAD) {
-        const int64_t at = base + (int64_t)threadIdx.x * nfs::SCAN_PER_THREAD;
-        uint32_t v[nfs::SCAN_PER_THREAD], sum = 0;
-#pragma unroll
-        for (int q = 0; q < nfs::SCAN_PER_THREAD; ++q) {
-            v[q] = at + q < n_blocks ? a[at + q] : 0u;
-            sum += v[q];
-        }
-        uint32_t total;
-        uint32_t run = carry + nf_iso_block_scan<nfs::SCAN_WAVES>(sum, s_wave, &total) - sum;
-#pragma unroll
-        for (int q = 0; q < nfs::SCAN_PER_THREAD; ++q) {
-            if (at + q < n_blocks) a[at + q] = run;
-            run += v[q];
-        }
-        carry += total;
-    }
+    __shared__ uint32_t s_wave[nfc::SCAN_WAVES];
+    const uint32_t carry = nf_scan_block_sums<nfg::SCAN_PER_THREAD>(a, n_blocks, s_wave);
     if (threadIdx.x == 0) {
         header[2] = (long long)carry;
         counts_out[0] = header[0];
@@ -232,12 +183,12 @@ __global__ void __launch_bounds__(nfs::SCAN_THREADS) k_sg_scan(uint32_t* __restr
     }
 }
 
-__global__ void __launch_bounds__(nfs::THREADS) k_sg_emit(float* __restrict__ grid, NfSgDims d, NfSgBox box, int64_t n_points,
+__global__ void __launch_bounds__(nfc::THREADS) k_sg_emit(float* __restrict__ grid, NfSgDims d, NfGridBox box, int64_t n_points,
                                                           const uint8_t* __restrict__ active, const uint8_t* __restrict__ side,
                                                           const uint32_t* __restrict__ block_base, int* __restrict__ index_out,
                                                           float* __restrict__ coords_out, int64_t capacity) {
-    __shared__ uint32_t s_wave[nfs::WAVES];
-    const int64_t p = (int64_t)blockIdx.x * nfs::THREADS + threadIdx.x;
+    __shared__ uint32_t s_wave[nfc::WAVES];
+    const int64_t p = (int64_t)blockIdx.x * nfc::THREADS + threadIdx.x;
     NfIsoPoint g = {0, 0, 0};
     int what = NF_SG_KEEP;
     if (p < n_points) {
@@ -246,37 +197,35 @@ __global__ void __launch_bounds__(nfs::THREADS) k_sg_emit(float* __restrict__ gr
     }
     const uint32_t flag = what == NF_SG_EVAL ? 1u : 0u;
     uint32_t total;
-    const int64_t slot = (int64_t)block_base[blockIdx.x] + nf_iso_block_scan<nfs::WAVES>(flag, s_wave, &total) - flag;
+    const int64_t slot = (int64_t)block_base[blockIdx.x] + nf_block_scan<nfc::WAVES>(flag, s_wave, &total) - flag;
     if (what == NF_SG_EVAL) {
         if (slot < capacity) {
             index_out[slot] = (int)p;
-            coords_out[slot * 3 + 0] = nf_sg_coord(box.lo[0], box.h[0], g.i);
-            coords_out[slot * 3 + 1] = nf_sg_coord(box.lo[1], box.h[1], g.j);
-            coords_out[slot * 3 + 2] = nf_sg_coord(box.lo[2], box.h[2], g.k);
+            coords_out[slot * 3 + 0] = nf_grid_coord(box.lo[0], box.h[0], g.i);
+            coords_out[slot * 3 + 1] = nf_grid_coord(box.lo[1], box.h[1], g.j);
+            coords_out[slot * 3 + 2] = nf_grid_coord(box.lo[2], box.h[2], g.k);
         }
     } else if (what != NF_SG_KEEP) {
         grid[p] = what == NF_SG_INSIDE ? __builtin_inff() : -__builtin_inff();
     }
 }
 
-__global__ void __launch_bounds__(nfs::THREADS) k_sg_scatter(const float* __restrict__ values, const int* __restrict__ index, int64_t count,
+__global__ void __launch_bounds__(nfc::THREADS) k_sg_scatter(const float* __restrict__ values, const int* __restrict__ index, int64_t count,
                                                              float* __restrict__ grid, int64_t n_points) {
-    const int64_t t = (int64_t)blockIdx.x * nfs::THREADS + threadIdx.x;
+    const int64_t t = (int64_t)blockIdx.x * nfc::THREADS + threadIdx.x;
     if (t >= count) return;
     const int64_t p = index[t];
     if (p >= 0 && p < n_points) grid[p] = values[t];             // an index that is none of the grid's writes nothing
 }
 
 // ---- entry points
-static inline unsigned nf_sg_blocks(int64_t n) { return (unsigned)((n + nfs::THREADS - 1) / nfs::THREADS); }
-
 extern "C" int nf_sparse_grid_lattice(int nx, int ny, int nz, int brick, const float* lo, const float* hi, int* index, float* coords,
                                       int64_t capacity, nf_stream_t stream) {
     NfSgPlan p;
-    NfSgBox box;
-    if (!lo || !hi || !index || !coords || !nf_sg_plan(nx, ny, nz, brick, &p) || capacity < p.n_lattice || !nf_sg_box(lo, hi, p.d, &box))
+    NfGridBox box;
+    if (!lo || !hi || !index || !coords || !nf_sg_plan(nx, ny, nz, brick, &p) || capacity < p.n_lattice || !nf_grid_box(lo, hi, nx, ny, nz, &box))
         return NF_EINVAL;
-    hipLaunchKernelGGL(k_sg_lattice, dim3(nf_sg_blocks(p.n_lattice)), dim3(nfs::THREADS), 0, nf_s(stream), p.d, box, p.n_lattice, index, coords);
+    hipLaunchKernelGGL(k_sg_lattice, dim3((unsigned)nf_blocks(p.n_lattice)), dim3(nfc::THREADS), 0, nf_s(stream), p.d, box, p.n_lattice, index, coords);
     NF_RETURN_LAUNCH();
 }
 
@@ -287,14 +236,14 @@ extern "C" int nf_sparse_grid_classify(const float* grid, int nx, int ny, int nz
     char* ws = static_cast<char*>(workspace);
     unsigned long long* header = reinterpret_cast<unsigned long long*>(ws);
     uint8_t* seed = reinterpret_cast<uint8_t*>(ws + p.off_seed);
-    const hipError_t e = hipMemsetAsync(ws, 0, nfs::HEADER, nf_s(stream));
+    const hipError_t e = hipMemsetAsync(ws, 0, nfc::HEADER, nf_s(stream));
     if (e != hipSuccess) return (int)e;
     const int reach = p.d.m[0] > p.d.m[1] ? (p.d.m[0] > p.d.m[2] ? p.d.m[0] : p.d.m[2]) : (p.d.m[1] > p.d.m[2] ? p.d.m[1] : p.d.m[2]);
     if (dilate > reach) dilate = reach;                          // covers the grid already, and brick index + dilate stays an int
-    const unsigned blocks = nf_sg_blocks(p.n_bricks);
-    hipLaunchKernelGGL(k_sg_classify, dim3(blocks), dim3(nfs::THREADS), 0, nf_s(stream), grid, p.d, level + margin, level - margin, p.n_bricks, seed,
+    const unsigned blocks = (unsigned)nf_blocks(p.n_bricks);
+    hipLaunchKernelGGL(k_sg_classify, dim3(blocks), dim3(nfc::THREADS), 0, nf_s(stream), grid, p.d, level + margin, level - margin, p.n_bricks, seed,
                        reinterpret_cast<uint8_t*>(ws + p.off_side), header);
-    hipLaunchKernelGGL(k_sg_dilate, dim3(blocks), dim3(nfs::THREADS), 0, nf_s(stream), seed, p.d, dilate, p.n_bricks,
+    hipLaunchKernelGGL(k_sg_dilate, dim3(blocks), dim3(nfc::THREADS), 0, nf_s(stream), seed, p.d, dilate, p.n_bricks,
                        reinterpret_cast<uint8_t*>(ws + p.off_active), header);
     NF_RETURN_LAUNCH();
 }
@@ -305,9 +254,9 @@ extern "C" int nf_sparse_grid_mark(int nx, int ny, int nz, int brick, void* work
     if (!workspace || !counts_dev || !nf_sg_plan(nx, ny, nz, brick, &p) || workspace_bytes < p.bytes) return NF_EINVAL;
     char* ws = static_cast<char*>(workspace);
     uint32_t* block = reinterpret_cast<uint32_t*>(ws + p.off_block);
-    hipLaunchKernelGGL(k_sg_count, dim3((unsigned)p.n_blocks), dim3(nfs::THREADS), 0, nf_s(stream), p.d, p.n_points,
+    hipLaunchKernelGGL(k_sg_count, dim3((unsigned)p.n_blocks), dim3(nfc::THREADS), 0, nf_s(stream), p.d, p.n_points,
                        reinterpret_cast<const uint8_t*>(ws + p.off_active), reinterpret_cast<const uint8_t*>(ws + p.off_side), block);
-    hipLaunchKernelGGL(k_sg_scan, dim3(1), dim3(nfs::SCAN_THREADS), 0, nf_s(stream), block, p.n_blocks, reinterpret_cast<long long*>(ws),
+    hipLaunchKernelGGL(k_sg_scan, dim3(1), dim3(nfc::SCAN_THREADS), 0, nf_s(stream), block, p.n_blocks, reinterpret_cast<long long*>(ws),
                        reinterpret_cast<long long*>(counts_dev));
     NF_RETURN_LAUNCH();
 }
@@ -315,12 +264,12 @@ extern "C" int nf_sparse_grid_mark(int nx, int ny, int nz, int brick, void* work
 extern "C" int nf_sparse_grid_emit(float* grid, int nx, int ny, int nz, int brick, const float* lo, const float* hi, void* workspace,
                                    size_t workspace_bytes, int* index, float* coords, int64_t capacity, nf_stream_t stream) {
     NfSgPlan p;
-    NfSgBox box;
+    NfGridBox box;
     if (!grid || !lo || !hi || !workspace || !nf_sg_plan(nx, ny, nz, brick, &p) || workspace_bytes < p.bytes || capacity < 0 ||
-        (capacity > 0 && (!index || !coords)) || !nf_sg_box(lo, hi, p.d, &box))
+        (capacity > 0 && (!index || !coords)) || !nf_grid_box(lo, hi, nx, ny, nz, &box))
         return NF_EINVAL;
     char* ws = static_cast<char*>(workspace);
-    hipLaunchKernelGGL(k_sg_emit, dim3((unsigned)p.n_blocks), dim3(nfs::THREADS), 0, nf_s(stream), grid, p.d, box, p.n_points,
+    hipLaunchKernelGGL(k_sg_emit, dim3((unsigned)p.n_blocks), dim3(nfc::THREADS), 0, nf_s(stream), grid, p.d, box, p.n_points,
                        reinterpret_cast<const uint8_t*>(ws + p.off_active), reinterpret_cast<const uint8_t*>(ws + p.off_side),
                        reinterpret_cast<const uint32_t*>(ws + p.off_block), index, coords, capacity);
     NF_RETURN_LAUNCH();
@@ -328,9 +277,9 @@ extern "C" int nf_sparse_grid_emit(float* grid, int nx, int ny, int nz, int bric
 
 extern "C" int nf_sparse_grid_scatter(const float* values, const int* index, int64_t count, float* grid, int nx, int ny, int nz,
                                       nf_stream_t stream) {
-    int64_t n_points;
     if (count == 0) return 0;
-    if (!values || !index || !grid || !nf_sg_grid(nx, ny, nz, &n_points) || count < 0 || count > n_points) return NF_EINVAL;
-    hipLaunchKernelGGL(k_sg_scatter, dim3(nf_sg_blocks(count)), dim3(nfs::THREADS), 0, nf_s(stream), values, index, count, grid, n_points);
+    const int64_t n_points = nf_grid_points(nx, ny, nz);
+    if (!values || !index || !grid || !n_points || count < 0 || count > n_points) return NF_EINVAL;
+    hipLaunchKernelGGL(k_sg_scatter, dim3((unsigned)nf_blocks(count)), dim3(nfc::THREADS), 0, nf_s(stream), values, index, count, grid, n_points);
     NF_RETURN_LAUNCH();
 }

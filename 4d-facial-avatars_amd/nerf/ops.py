@@ -1239,6 +1239,14 @@ def _box(lo, hi, what: str):
     return lo32, hi32
 
 
+def _workspace(lib, fn_name, args, dev, message: str):
+    """(workspace on dev, its bytes) by the unit's size query; ValueError(message) for a size past its plan.  dev = None: no workspace, the check alone."""
+    ws_bytes = int(getattr(lib, fn_name)(*args))
+    if ws_bytes == 0:
+        raise ValueError(message)
+    return None if dev is None else torch.empty(ws_bytes, dtype=torch.uint8, device=dev), ws_bytes
+
+
 def isosurface(grid: torch.Tensor, level: float, lo, hi, normals: bool = False):
     """Triangle mesh of the surface grid == level inside the box [lo, hi]: grid (nz, ny, nx) float32 on a ROCm device, x fastest,
     grid point (i, j, k) at lo + (i, j, k) * (hi - lo) / (n - 1); a point is inside iff grid > level.  Marching tetrahedra on the
@@ -1255,11 +1263,8 @@ def isosurface(grid: torch.Tensor, level: float, lo, hi, normals: bool = False):
         raise ValueError(f"isosurface: every axis needs at least 2 grid points, got (nz, ny, nx) = {(nz, ny, nx)}")
     lo32, hi32 = _box(lo, hi, "isosurface")
     lib = H.lib()
-    ws_bytes = int(lib.nf_isosurface_workspace_bytes(nx, ny, nz))
-    if ws_bytes == 0:
-        raise ValueError(f"isosurface: a grid of {nx} x {ny} x {nz} points is past the plan of csrc/nf_isosurface.hip (7 * points and "
-                         "12 * cells stay below 2^31: vertex and face ids are int32)")
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    ws, ws_bytes = _workspace(lib, "nf_isosurface_workspace_bytes", (nx, ny, nz), dev, f"isosurface: a grid of {nx} x {ny} x {nz} points is past the plan "
+                              "of csrc/nf_isosurface.hip (7 * points and 12 * cells stay below 2^31: vertex and face ids are int32)")
     counts = torch.empty(2, dtype=torch.int64, device=dev)
     c_lo, c_hi = (C.c_float * 3)(*lo32.tolist()), (C.c_float * 3)(*hi32.tolist())
     with torch.cuda.device(dev):
@@ -1301,13 +1306,21 @@ def _check_faces(faces, n_vertices, what: str):
     return n_vertices, int(faces.shape[0])
 
 
-def _check_filter_args(vertices, faces, normals, largest, min_faces, what: str):
-    """Everything filter_mesh can refuse without a device; returns (V, F, largest, min_faces) with min_faces = 0 under `largest`."""
+def _check_vertices(vertices, what: str):
     if not torch.is_tensor(vertices) or vertices.dtype != torch.float32 or vertices.dim() != 2 or vertices.shape[1] != 3:
         raise ValueError(f"{what}: vertices must be a float32 tensor of shape (V, 3)")
-    n_vertices, n_faces = _check_faces(faces, vertices.shape[0], what)
+
+
+def _check_normals(normals, vertices, what: str):
     if normals is not None and (not torch.is_tensor(normals) or normals.dtype != torch.float32 or normals.shape != vertices.shape):
         raise ValueError(f"{what}: normals must be None or a float32 tensor of the vertices' shape {tuple(vertices.shape)}")
+
+
+def _check_filter_args(vertices, faces, normals, largest, min_faces, what: str):
+    """Everything filter_mesh can refuse without a device; returns (V, F, largest, min_faces) with min_faces = 0 under `largest`."""
+    _check_vertices(vertices, what)
+    n_vertices, n_faces = _check_faces(faces, vertices.shape[0], what)
+    _check_normals(normals, vertices, what)
     largest = bool(largest)
     if largest == (min_faces is not None):
         raise ValueError(f"{what}: exactly one rule applies, largest=True or min_faces=N")
@@ -1316,13 +1329,6 @@ def _check_filter_args(vertices, faces, normals, largest, min_faces, what: str):
             raise ValueError(f"{what}: min_faces is a whole number of at least 1, got {min_faces!r}")
         min_faces = int(min_faces)
     return n_vertices, n_faces, largest, min_faces or 0
-
-
-def _mesh_components_workspace(lib, n_vertices, n_faces, dev, what):
-    ws_bytes = int(lib.nf_mesh_components_workspace_bytes(n_vertices, n_faces))
-    if ws_bytes == 0:
-        raise ValueError(f"{what}: {n_vertices} vertices and {n_faces} faces are past the plan of csrc/nf_mesh_components.hip (both below 2^31)")
-    return torch.empty(ws_bytes, dtype=torch.uint8, device=dev), ws_bytes
 
 
 def _require_same_device(what, first, *others):
@@ -1334,13 +1340,15 @@ def _require_same_device(what, first, *others):
     return first.device
 
 
-def _label_mesh(lib, faces, n_vertices, n_faces, ws, ws_bytes, counts, dev):
-    """The launches of nf_mesh_components_label into fresh buffers (the counts hold V entries, of which C are written)."""
+def _label_mesh(lib, faces, n_vertices, n_faces, counts, dev, what):
+    """The workspace (returned first, with its bytes) and the launches of nf_mesh_components_label into fresh buffers (the counts hold V entries, C written)."""
+    ws, ws_bytes = _workspace(lib, "nf_mesh_components_workspace_bytes", (n_vertices, n_faces), dev,
+                              f"{what}: {n_vertices} vertices and {n_faces} faces are past the plan of csrc/nf_mesh_components.hip (both below 2^31)")
     i32 = lambda n: torch.empty(n, dtype=torch.int32, device=dev)
     vertex_label, face_label, face_counts, vertex_counts = i32(n_vertices), i32(n_faces), i32(n_vertices), i32(n_vertices)
     H.check(lib.nf_mesh_components_label(H.ptr(faces), n_vertices, n_faces, H.ptr(ws), ws_bytes, H.ptr(vertex_label), H.ptr(face_label),
                                          H.ptr(face_counts), H.ptr(vertex_counts), H.ptr(counts), H.stream_ptr(dev)), "nf_mesh_components_label")
-    return vertex_label, face_label, face_counts, vertex_counts
+    return (ws, ws_bytes), vertex_label, face_label, face_counts, vertex_counts
 
 
 def mesh_components(faces: torch.Tensor, n_vertices: int) -> MeshComponents:
@@ -1353,10 +1361,9 @@ def mesh_components(faces: torch.Tensor, n_vertices: int) -> MeshComponents:
     dev = _require_same_device("mesh_components", faces)
     faces = faces.detach().contiguous()
     lib = H.lib()
-    ws, ws_bytes = _mesh_components_workspace(lib, n_vertices, n_faces, dev, "mesh_components")
     counts = torch.empty(4, dtype=torch.int64, device=dev)
     with torch.cuda.device(dev):
-        vertex_label, face_label, face_counts, vertex_counts = _label_mesh(lib, faces, n_vertices, n_faces, ws, ws_bytes, counts, dev)
+        _, vertex_label, face_label, face_counts, vertex_counts = _label_mesh(lib, faces, n_vertices, n_faces, counts, dev, "mesh_components")
         n_components = int(counts[0].item())                            # the one host read
     return MeshComponents(vertex_label, face_label, face_counts[:n_components].clone(), vertex_counts[:n_components].clone())
 
@@ -1373,11 +1380,10 @@ def filter_mesh(vertices: torch.Tensor, faces: torch.Tensor, normals: Optional[t
     vertices, faces = vertices.detach().contiguous(), faces.detach().contiguous()
     normals = None if normals is None else normals.detach().contiguous()
     lib = H.lib()
-    ws, ws_bytes = _mesh_components_workspace(lib, n_vertices, n_faces, dev, "filter_mesh")
     counts = torch.empty(4, dtype=torch.int64, device=dev)
     with torch.cuda.device(dev):
         stream = H.stream_ptr(dev)
-        vertex_label, face_label, face_counts, _ = _label_mesh(lib, faces, n_vertices, n_faces, ws, ws_bytes, counts, dev)
+        (ws, ws_bytes), vertex_label, face_label, face_counts, _ = _label_mesh(lib, faces, n_vertices, n_faces, counts, dev, "filter_mesh")
         H.check(lib.nf_mesh_components_select(H.ptr(vertex_label), H.ptr(face_label), H.ptr(face_counts), n_vertices, n_faces, int(largest), min_faces,
                                               H.ptr(ws), ws_bytes, H.ptr(counts), stream), "nf_mesh_components_select")
         n_components, kept_v, kept_f, kept_c = counts.tolist()          # the one host read
@@ -1416,8 +1422,7 @@ def _check_smooth_sizes(n_vertices, n_faces, what: str):
 
 
 def _check_smooth_mesh(vertices, faces, what: str):
-    if not torch.is_tensor(vertices) or vertices.dtype != torch.float32 or vertices.dim() != 2 or vertices.shape[1] != 3:
-        raise ValueError(f"{what}: vertices must be a float32 tensor of shape (V, 3)")
+    _check_vertices(vertices, what)
     n_vertices, n_faces = _check_faces(faces, vertices.shape[0], what)
     _check_smooth_sizes(n_vertices, n_faces, what)
     return n_vertices, n_faces
@@ -1426,8 +1431,7 @@ def _check_smooth_mesh(vertices, faces, what: str):
 def _check_smooth_args(vertices, faces, normals, iterations, lam, mu, what: str):
     """Everything smooth_mesh can refuse without a device; returns (V, F, iterations, lam, mu), the factors rounded to float32."""
     n_vertices, n_faces = _check_smooth_mesh(vertices, faces, what)
-    if normals is not None and (not torch.is_tensor(normals) or normals.dtype != torch.float32 or normals.shape != vertices.shape):
-        raise ValueError(f"{what}: normals must be None or a float32 tensor of the vertices' shape {tuple(vertices.shape)}")
+    _check_normals(normals, vertices, what)
     try:
         whole = not isinstance(iterations, bool) and int(iterations) == iterations and 0 <= int(iterations) < 2 ** 30
     except (TypeError, ValueError, OverflowError):
@@ -1444,10 +1448,8 @@ def _check_smooth_args(vertices, faces, normals, iterations, lam, mu, what: str)
 
 
 def _mesh_smooth_workspace(lib, n_vertices, n_faces, dev, what):
-    ws_bytes = int(lib.nf_mesh_smooth_workspace_bytes(n_vertices, n_faces))
-    if ws_bytes == 0:
-        raise ValueError(f"{what}: {n_vertices} vertices and {n_faces} faces are past the plan of csrc/nf_mesh_smooth.hip (V and 6 F below 2^31)")
-    return torch.empty(ws_bytes, dtype=torch.uint8, device=dev), ws_bytes
+    return _workspace(lib, "nf_mesh_smooth_workspace_bytes", (n_vertices, n_faces), dev,
+                      f"{what}: {n_vertices} vertices and {n_faces} faces are past the plan of csrc/nf_mesh_smooth.hip (V and 6 F below 2^31)")
 
 
 def _adjacency(lib, faces, n_vertices, n_faces, dev):
@@ -1585,10 +1587,8 @@ def sparse_grid(fn, level: float, lo, hi, resolution, *, brick: int = 8, margin:
     lo32, hi32 = _box(lo, hi, "sparse_grid")
     lib = H.lib()
     b = min(brick, 0x7fffffff)
-    ws_bytes = int(lib.nf_sparse_grid_workspace_bytes(nx, ny, nz, b))
-    if ws_bytes == 0:
-        raise ValueError(f"sparse_grid: a grid of {nx} x {ny} x {nz} points is past the plan of csrc/nf_isosurface.hip (7 * points and "
-                         "12 * cells stay below 2^31: vertex and face ids are int32)")
+    _, ws_bytes = _workspace(lib, "nf_sparse_grid_workspace_bytes", (nx, ny, nz, b), None, f"sparse_grid: a grid of {nx} x {ny} x {nz} points is past the plan "
+                             "of csrc/nf_isosurface.hip (7 * points and 12 * cells stay below 2^31: vertex and face ids are int32)")
     if not torch.cuda.is_available():
         raise RuntimeError("nerf (MI355X build): sparse_grid runs on a ROCm device; there is no CPU path in this package")
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)

@@ -18,7 +18,7 @@ from tests import util as U
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BLOCK = 256                    # nfi::THREADS: points per workgroup, one block sum each
+BLOCK = 256                    # nfc::THREADS: points per workgroup, one block sum each
 SCAN_ROUND = 16 * 1024         # k_iso_scan: block sums per round of its one workgroup (SCAN_PER_THREAD * SCAN_THREADS)
 
 # (nx, ny, nz).  (41, 5, 5) = 1025 points: one more than four workgroups' 4 * 256, so the last point sits alone in a fifth workgroup,
@@ -27,8 +27,8 @@ SMALL_GRIDS = [(2, 2, 2), (3, 2, 2), (65, 3, 2), (257, 2, 2), (23, 19, 21), (41,
 
 
 def test_the_constants_above_are_the_kernels_own():
-    text = open(os.path.join(ROOT, "4d-facial-avatars_amd", "csrc", "nf_isosurface.hip")).read()
-    assert "constexpr int THREADS = 256;" in text and "constexpr int SCAN_THREADS = 1024;" in text and "constexpr int SCAN_PER_THREAD = 16;" in text
+    shared, unit = (open(os.path.join(ROOT, "4d-facial-avatars_amd", "csrc", f)).read() for f in ("nf_scan_dev.h", "nf_isosurface.hip"))
+    assert "constexpr int THREADS = 256;" in shared and "constexpr int SCAN_THREADS = 1024;" in shared and "constexpr int SCAN_PER_THREAD = 16;" in unit
     assert 41 * 5 * 5 == 4 * BLOCK + 1
 
 

@@ -17,14 +17,14 @@ from tests import util as U
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BLOCK = 256                    # nfm::THREADS: vertices or faces per workgroup, one block sum each
+BLOCK = 256                    # nfc::THREADS: vertices or faces per workgroup, one block sum each
 SCAN_ROUND = 4 * 1024          # k_mc_scan: block sums per round of its one workgroup (SCAN_PER_THREAD * SCAN_THREADS)
 SCAN_CAPACITY = SCAN_ROUND * BLOCK     # vertices (or faces) whose block sums one round takes: 2^20
 
 
 def test_the_constants_above_are_the_kernels_own():
-    text = open(os.path.join(ROOT, "4d-facial-avatars_amd", "csrc", "nf_mesh_components.hip")).read()
-    assert "constexpr int THREADS = 256;" in text and "constexpr int SCAN_THREADS = 1024;" in text and "constexpr int SCAN_PER_THREAD = 4;" in text
+    shared, unit = (open(os.path.join(ROOT, "4d-facial-avatars_amd", "csrc", f)).read() for f in ("nf_scan_dev.h", "nf_mesh_components.hip"))
+    assert "constexpr int THREADS = 256;" in shared and "constexpr int SCAN_THREADS = 1024;" in shared and "constexpr int SCAN_PER_THREAD = 4;" in unit
     assert SCAN_CAPACITY == 1 << 20
 
 

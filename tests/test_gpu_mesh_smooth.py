@@ -192,9 +192,9 @@ def test_one_triangle_stays_under_fix_boundary_and_moves_without(hip_lib, gpu):
 # ---- 2. row paths: one thread up to SHORT_ROW entries of the unsorted row, one wave past it
 def test_the_threshold_above_is_the_kernels_own():
     from nerf import ops
-    text = open(os.path.join(ROOT, "4d-facial-avatars_amd", "csrc", "nf_mesh_smooth.hip")).read()
-    assert f"constexpr int SHORT_ROW = {ops.MESH_SMOOTH_SHORT_ROW};" in text and "constexpr int THREADS = 256;" in text
-    assert "constexpr int SCAN_THREADS = 1024;" in text and "constexpr int SCAN_PER_THREAD = 4;" in text and ops.MESH_SMOOTH_SHORT_ROW % 2 == 0
+    shared, unit = (open(os.path.join(ROOT, "4d-facial-avatars_amd", "csrc", f)).read() for f in ("nf_scan_dev.h", "nf_mesh_smooth.hip"))
+    assert f"constexpr int SHORT_ROW = {ops.MESH_SMOOTH_SHORT_ROW};" in unit and "constexpr int THREADS = 256;" in shared
+    assert "constexpr int SCAN_THREADS = 1024;" in shared and "constexpr int SCAN_PER_THREAD = 4;" in unit and ops.MESH_SMOOTH_SHORT_ROW % 2 == 0
 
 
 @pytest.mark.parametrize("order", ["ascending", "descending", "permuted"])
