@@ -129,8 +129,12 @@ static inline int nf_pack_split_bf16(NfPackTable& cache, Build build, const floa
 
 // ---- fp16 split streams (nf_mlp_f16.hip): x = hi + lo in fp16 keeps 22 significand bits, but fp16's exponent range is
 // narrow, so every layer's weights are multiplied by a power of two 2^e chosen from the layer's largest |w| such that the
-// scaled maximum lies in [2^13, 2^14): the `lo` parts (<= 2^-11 of the value) then stay normal fp16 numbers for every
-// weight down to 2^-17 of the layer's largest.  Tail of the stream buffer (NF_F16_TAIL_BYTES behind the blocks):
+// scaled maximum lies in [2^13, 2^14).  `lo` is the fp16 rounding of the residual w 2^e - hi (<= 2^-11 of the value, about
+// 2^-12 of it on average): a normal fp16 number for the weights of a typical layer, a subnormal one (quantum 2^-24, kept by
+// the conversion) for scaled weights below about 2^0, and always subnormal or zero below 2^-3.  So hi + lo is within 2^-22
+// relative of every scaled weight of magnitude >= 2^-3 -- 2^-17 of the window's top 2^14, i.e. weights down to 2^-16 ..
+// 2^-17 of the layer's largest, depending on where that sits in the window -- and within 2^-25 absolute (scaled units) of
+// every smaller one (tests/test_split_stream_host.py).  Tail of the stream buffer (NF_F16_TAIL_BYTES behind the blocks):
 // [NL] bias scales s_W * act_scale | [NL] inverse weight scales 1 / s_W | [NL] scratch (|w| maxima as uint bits) | ... |
 // dword NF_F16_FLAG_WORD: range-guard flag set by the forward kernel.
 #define NF_F16_TAIL_BYTES 256
