@@ -4,7 +4,8 @@ launch/eval_sharded.py picks them), the raw density on a dense grid (nerf.densit
 
     python -m launch.extract_mesh --config cfg.yml --checkpoint ck --frame I --level L --resolution N [Ny Nz] --out mesh.ply \
         [--bounds x0 y0 z0 x1 y1 z1] [--precision f32|f16x3|f16x2|bf16x3] [--coarse] [--brick B [--margin M] [--dilate D]] \
-        [--largest | --min-faces N] [--smooth N [--smooth-lambda L] [--smooth-mu M]]
+        [--largest | --min-faces N] [--smooth N [--smooth-lambda L] [--smooth-mu M]] \
+        [--colour [--colour-samples K] [--colour-depth D] [--colour-view-z Z]]
 
 Without --bounds the box is the axis-aligned hull of the frame's camera frustum between the config's near and far planes (the
 four image-corner rays of nerf.get_ray_bundle).  --level is in raw-density units (before the renderer's ReLU) and has no default.
@@ -14,7 +15,10 @@ within --dilate bricks of those.  A feature thinner than a brick that passes bet
 --largest keeps the connected component with the most faces, --min-faces N every component with at least N faces (nerf.filter_mesh,
 on the device): a trained model's floaters are small components of their own.  --smooth N runs N iterations of Taubin's lambda | mu
 smoothing on what is left (nerf.smooth_mesh, on the device; the border a box cuts into the surface stays where it is) and writes
-the normals of the smoothed faces in place of the density gradient's.
+the normals of the smoothed faces in place of the density gradient's.  --colour writes a colour per vertex of that final mesh
+(nerf.vertex_colours, from the same network as the density): K samples (default 8) on a ray along the normal through a shell of
+half-thickness D round the surface (default: the diagonal of a grid cell), composited and normalised, seen from the frame's camera
+(its pose and the config's near / far), or with the view direction (0, 0, Z) under --colour-view-z.
 """
 from __future__ import annotations
 
@@ -65,6 +69,10 @@ def _main(argv=None):
     ap.add_argument("--smooth", type=int, default=0, metavar="N", help="iterations of Taubin smoothing after the component filter (default: none)")
     ap.add_argument("--smooth-lambda", type=float, default=0.5, metavar="L", help="with --smooth: the shrinking factor, 0 < L <= 1")
     ap.add_argument("--smooth-mu", type=float, default=-0.53, metavar="M", help="with --smooth: the inflating factor, -1 <= M <= 0 (0: plain Laplacian smoothing)")
+    ap.add_argument("--colour", action="store_true", help="write a colour per vertex of the final mesh, from the same network as the density")
+    ap.add_argument("--colour-samples", type=int, default=8, metavar="K", help="with --colour: samples on the ray through every vertex, 1 .. 64")
+    ap.add_argument("--colour-depth", type=float, default=None, metavar="D", help="with --colour: half-thickness of the sampled shell (default: a grid cell's diagonal)")
+    ap.add_argument("--colour-view-z", type=float, default=None, metavar="Z", help="with --colour: the view direction (0, 0, Z) in place of the frame's camera")
     args = ap.parse_args(argv)
     if len(args.resolution) not in (1, 3):
         ap.error("--resolution takes one number or three")
@@ -76,6 +84,8 @@ def _main(argv=None):
         ap.error("--min-faces takes at least 1")
     if args.smooth < 0 or not 0.0 < args.smooth_lambda <= 1.0 or not -1.0 <= args.smooth_mu <= 0.0:
         ap.error("--smooth takes at least 0 iterations, --smooth-lambda a factor in (0, 1] and --smooth-mu one in [-1, 0]")
+    if not 1 <= args.colour_samples <= ops.MESH_COLOUR_MAX_SAMPLES or (args.colour_depth is not None and not args.colour_depth >= 0.0):
+        ap.error(f"--colour-samples takes 1 to {ops.MESH_COLOUR_MAX_SAMPLES} samples and --colour-depth at least 0")
     if not torch.cuda.is_available():
         raise SystemExit("the MI355X `nerf` package needs a ROCm device")
     dev = torch.device("cuda", torch.cuda.current_device())
@@ -127,9 +137,22 @@ def _main(argv=None):
     if args.smooth:
         *smoothed, smooth = ops.smooth_mesh(*mesh, iterations=args.smooth, lam=args.smooth_lambda, mu=args.smooth_mu)
         mesh = nerf.Mesh(*smoothed)
+    colour = None
+    if args.colour:
+        cell = [(float(h) - float(l)) / (int(n) - 1) for l, h, n in zip(lo, hi, res)]
+        depth = args.colour_depth if args.colour_depth is not None else float(np.sqrt(sum(c * c for c in cell)))
+        view = dict(view_z=args.colour_view_z) if args.colour_view_z is not None else dict(pose=poses[args.frame, :3, :4].float().to(dev))
+        min_opacity = 1e-3
+        colours = nerf.vertex_colours(model, mesh, expr, latent, near=float(cfg.dataset.near), far=float(cfg.dataset.far), samples=args.colour_samples,
+                                      depth=depth, min_opacity=min_opacity, **view)
+        colour = {"vertices": int(mesh.vertices.shape[0]), "samples": args.colour_samples, "depth": depth, "min_opacity": min_opacity,
+                  "below_min_opacity": int((~(colours.opacity >= min_opacity)).sum().item())}       # the one host read
     torch.cuda.synchronize()
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    nerf.write_mesh(args.out, mesh)
+    if colour is None:
+        nerf.write_mesh(args.out, mesh)
+    else:
+        nerf.write_mesh(args.out, mesh, colours=colours.colours)
     stats = {"lo": [float(x) for x in lo], "hi": [float(x) for x in hi], "resolution": [int(r) for r in res], "vertices": int(mesh.vertices.shape[0]),
              "faces": int(mesh.faces.shape[0]), "density_s": ev[0].elapsed_time(ev[1]) * 1e-3, "extract_s": ev[1].elapsed_time(ev[2]) * 1e-3,
              "network": "coarse" if model is model_c else "fine", "out": args.out}
@@ -144,6 +167,10 @@ def _main(argv=None):
         stats["smooth"] = smooth._asdict()
         print(f"smoothed: {args.smooth} iterations (lambda {args.smooth_lambda}, mu {args.smooth_mu}) in {smooth.passes} passes over {smooth.edges // 2} edges; "
               f"{smooth.pinned_vertices} boundary vertices of {stats['vertices']} stay where they are")
+    if colour is not None:
+        stats["colour"] = colour
+        print(f"coloured: {colour['vertices']} vertices, {colour['samples']} samples over a shell of half-thickness {colour['depth']:.6g}; "
+              f"{colour['below_min_opacity']} vertices below opacity {colour['min_opacity']:g} take the colour of the sample at the vertex")
     if sparse is not None:
         stats["sparse"] = sparse._asdict()
         print(f"bricks of {args.brick} cells (margin {args.margin}, dilate {args.dilate}): {sparse.seed_bricks} seed and {sparse.active_bricks} active of "

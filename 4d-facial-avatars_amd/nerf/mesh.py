@@ -7,12 +7,16 @@
     filter_mesh(mesh, largest= | min_faces=)                               -> the Mesh of the largest component, or of those of >= N faces
     smooth_mesh(mesh, iterations=, lam=, mu=, fix_boundary=)               -> the Mesh after Taubin smoothing, its normals recomputed
     vertex_normals(mesh)                                                   -> (V, 3) unit normals from the faces
-    write_mesh(path, mesh)                                                 -> .off / .obj / .ply (binary little-endian), host code
+    vertex_colours(model, mesh, expr, latent_code, near=, far=, pose= | view_z=, samples=, depth=)
+                                                                           -> MeshColours(colours (V, 3) in [0, 1], opacity (V,))
+    write_mesh(path, mesh, colours=None)                                   -> .off / .obj / .ply (binary little-endian), host code
 
 The density comes from the density-only kernels (nerf.density), the surface from ops.isosurface (csrc/nf_isosurface.hip), the choice
 of the points near the surface from ops.sparse_grid (csrc/nf_sparse_grid.hip), the components from ops.mesh_components and
 ops.filter_mesh (csrc/nf_mesh_components.hip), smoothing and face normals from ops.smooth_mesh and ops.vertex_normals
-(csrc/nf_mesh_smooth.hip).
+(csrc/nf_mesh_smooth.hip).  The colours come from the model's full forward (the network nerf.radiance queries) on a short ray through
+the surface at every vertex, along the normal, composited and normalised by ops.mesh_colour_rays and ops.mesh_colour_integrate
+(csrc/nf_mesh_colour.hip; DESIGN.md "Mesh colours"); write_mesh stores them per vertex in each of its three formats.
 """
 from __future__ import annotations
 
@@ -23,7 +27,8 @@ import numpy as np
 import torch
 
 from . import ops
-from .models import density
+from .models import _point_query, density
+from .ops import MeshColours
 
 
 class Mesh(NamedTuple):
@@ -153,6 +158,45 @@ def extract_mesh(model, expr, latent_code=None, *, lo, hi, resolution, level, no
     return smooth_mesh(mesh, iterations=int(smooth), lam=smooth_lam, mu=smooth_mu) if int(smooth) else mesh
 
 
+def vertex_colours(model, mesh, expr, latent_code=None, *, near, far, pose=None, view_z=None, samples: int = 8, depth, min_opacity: float = 1e-3,
+                   chunk_points: int = 1 << 22) -> MeshColours:
+    """The colour of every vertex of a Mesh (or a (vertices, faces[, normals]) tuple; without normals, vertex_normals(mesh) are used)
+    under a fused model's radiance field, for one expression (and latent code): MeshColours(colours (V, 3) float32 in [0, 1],
+    opacity (V,) float32).  Through every vertex runs a ray along the inward normal with `samples` samples spread over the shell
+    [-depth, +depth] round the surface (ops.mesh_colour_rays); the model's full forward (model.hip_forward, the arithmetic of
+    nerf.set_mlp_precision; never live_only) gives colour and density there, and ops.mesh_colour_integrate composites them from
+    outside to inside as the renderer does and divides by the opacity gathered -- the colour a camera just outside the surface sees,
+    without the background the camera-ray integrator ends on.  Where the shell absorbs less than `min_opacity` the colour is that
+    of the sample at the vertex (samples // 2).
+
+    `depth`, in world units, has no default: how far the true surface can lie from a vertex depends on the grid cell the mesh was
+    extracted on and on how much it was smoothed (the length of a cell's diagonal is what launch/extract_mesh.py takes).  Under
+    Quirk Q1 the network's direction input is PE4(view z, near, far): `near` and `far` are the config's, and the view direction is
+    either that of the camera `pose` (camera-to-world, (3, 4) or (4, 4) on the device: every vertex gets the direction of the pixel
+    that sees it, a vertex behind the camera the central ray) or (0, 0, view_z) -- exactly one of the two.
+
+    Inference only, under torch.no_grad(); nerf.density's guards, one weight pack per call, the split-fp16 range check after it.  In
+    slabs of max(1, chunk_points // samples) whole vertices; the same bits for any chunk_points.  No vertices: nothing is launched."""
+    vertices, faces, normals = _mesh_fields(mesh, "vertex_colours")
+    if not torch.is_tensor(vertices) or vertices.dim() != 2 or vertices.shape[1] != 3:
+        raise ValueError("vertex_colours: vertices must be a tensor of shape (V, 3)")
+    samples, depth, _ = ops._check_colour_args(samples, depth, pose, view_z, "vertex_colours")
+    with torch.no_grad():
+        expr, latent = _point_query(model, vertices, expr, latent_code, "vertex_colours")
+        if vertices.shape[0] == 0:
+            return MeshColours(torch.empty((0, 3), dtype=torch.float32, device=vertices.device), torch.empty((0,), dtype=torch.float32, device=vertices.device))
+        if normals is None:
+            normals = ops.vertex_normals(vertices, faces)
+        ops.bump_pack_epoch()          # as nerf.density: a weight image never outlives one call
+        near, far = float(near), float(far)
+        forward = lambda ro, rd, z, rd_view: model.hip_forward(ro, rd, z, rd_view, expr, latent, near, far, need_grad=False)[0]
+        out = ops.vertex_colours(forward, vertices, normals, samples=samples, depth=depth, pose=pose, view_z=view_z, min_opacity=min_opacity,
+                                 chunk_points=chunk_points)
+        if ops.get_mlp_precision() in ops.F16_MODES:
+            ops.check_f16_range(model)
+    return out
+
+
 def _host(mesh):
     v, f, n = (tuple(mesh) + (None,))[:3]
     to = lambda t, dt: None if t is None else np.ascontiguousarray((t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)), dtype=dt)
@@ -162,20 +206,53 @@ def _host(mesh):
     return v, f, n
 
 
-def write_mesh(path: str, mesh) -> None:
+def quantise_colours(colours) -> np.ndarray:
+    """(V, 3) uint8 of float colours by the rule the rendered frames are written with (cast_to_image): clip to [0, 1], times 255 in
+    float32, truncate; a NaN becomes 0.  uint8 input is returned as it is."""
+    c = np.asarray(colours)
+    if c.dtype == np.uint8:
+        return np.ascontiguousarray(c)
+    c = np.nan_to_num(c.astype(np.float32), nan=0.0)
+    return (np.clip(c, np.float32(0), np.float32(1)) * np.float32(255)).astype(np.uint8)
+
+
+def _host_colours(colours, n_vertices):
+    """(floats (V, 3) float32 for the text formats, bytes (V, 3) uint8) of write_mesh's colours."""
+    c = colours.detach().cpu().numpy() if torch.is_tensor(colours) else np.asarray(colours)
+    if c.shape != (n_vertices, 3) or not (c.dtype == np.uint8 or np.issubdtype(c.dtype, np.floating)):
+        raise ValueError(f"write_mesh: colours must be ({n_vertices}, 3), the vertices' shape, float in [0, 1] or uint8, got {c.dtype} {c.shape}")
+    as_float = c.astype(np.float32) / np.float32(255) if c.dtype == np.uint8 else c.astype(np.float32)
+    return as_float, quantise_colours(c)
+
+
+def write_mesh(path: str, mesh, colours=None) -> None:
     """Write Mesh(vertices, faces, normals) -- or a (vertices, faces[, normals]) tuple -- in the format the extension names: .off
     (positions and faces; floats printed with 9 significant digits, which round-trips float32), .obj (`vn` lines and `f a//a`
-    indices when there are normals) or .ply (binary little-endian: float x y z [nx ny nz], then uchar 3 + three int32 per face)."""
+    indices when there are normals) or .ply (binary little-endian: float x y z [nx ny nz], then uchar 3 + three int32 per face).
+
+    colours: None, or (V, 3) per-vertex colours (nerf.vertex_colours), a tensor or an array, float in [0, 1] or uint8.  Floats are
+    quantised by the rule the rendered frames are written with (cast_to_image): clip to [0, 1], multiply by 255 in float32,
+    truncate.  .ply: `property uchar red / green / blue` behind the normals, if any; .obj: `v x y z r g b` with the floats as they
+    are, 9 significant digits (uint8 divided by 255); .off: the header becomes COFF and a vertex line `x y z r g b 255` with the
+    bytes.  Without colours every format is what it was, byte for byte."""
     v, f, n = _host(mesh)
+    if colours is not None:
+        c_float, c_byte = _host_colours(colours, len(v))
     ext = os.path.splitext(path)[1].lower()
     if ext == ".off":
         with open(path, "w") as fh:
-            fh.write(f"OFF\n{len(v)} {len(f)} 0\n")
-            fh.writelines("%.9g %.9g %.9g\n" % tuple(p) for p in v.tolist())
+            fh.write(f"{'OFF' if colours is None else 'COFF'}\n{len(v)} {len(f)} 0\n")
+            if colours is None:
+                fh.writelines("%.9g %.9g %.9g\n" % tuple(p) for p in v.tolist())
+            else:
+                fh.writelines("%.9g %.9g %.9g %d %d %d 255\n" % (*p, *c) for p, c in zip(v.tolist(), c_byte.tolist()))
             fh.writelines("3 %d %d %d\n" % tuple(t) for t in f.tolist())
     elif ext == ".obj":
         with open(path, "w") as fh:
-            fh.writelines("v %.9g %.9g %.9g\n" % tuple(p) for p in v.tolist())
+            if colours is None:
+                fh.writelines("v %.9g %.9g %.9g\n" % tuple(p) for p in v.tolist())
+            else:
+                fh.writelines("v %.9g %.9g %.9g %.9g %.9g %.9g\n" % (*p, *c) for p, c in zip(v.tolist(), c_float.tolist()))
             if n is not None:
                 fh.writelines("vn %.9g %.9g %.9g\n" % tuple(p) for p in n.tolist())
                 fh.writelines("f %d//%d %d//%d %d//%d\n" % (a, a, b, b, c, c) for a, b, c in (f + 1).tolist())
@@ -184,12 +261,17 @@ def write_mesh(path: str, mesh) -> None:
     elif ext == ".ply":
         props = ["x", "y", "z"] + (["nx", "ny", "nz"] if n is not None else [])
         header = "ply\nformat binary_little_endian 1.0\n" + f"element vertex {len(v)}\n" + "".join(f"property float {p}\n" for p in props) + \
+                 ("" if colours is None else "".join(f"property uchar {p}\n" for p in ("red", "green", "blue"))) + \
                  f"element face {len(f)}\nproperty list uchar int vertex_indices\nend_header\n"
         rows = np.zeros(len(f), dtype=[("n", "u1"), ("i", "<i4", (3,))])
         rows["n"], rows["i"] = 3, f
+        floats = (v if n is None else np.concatenate([v, n], axis=1)).astype("<f4")
+        if colours is not None:
+            packed = np.zeros(len(v), dtype=[("f", "<f4", (floats.shape[1],)), ("c", "u1", (3,))])
+            packed["f"], packed["c"] = floats, c_byte
         with open(path, "wb") as fh:
             fh.write(header.encode("ascii"))
-            fh.write((v if n is None else np.concatenate([v, n], axis=1)).astype("<f4").tobytes())
+            fh.write(floats.tobytes() if colours is None else packed.tobytes())
             fh.write(rows.tobytes())
     else:
         raise ValueError(f"write_mesh: unknown extension {ext!r} (.off, .obj or .ply)")

@@ -96,13 +96,11 @@ class _FusedNeRFModel(torch.nn.Module):
         return ops.mlp_forward_encoded(self.hip_weights(), x, expr, latent_code)
 
 
-def density(model, points, expr, latent_code=None):
-    """Raw density (N,) of a fused model at arbitrary points (N, 3) for one expression (and latent code): raw[..., 3], before the
-    ReLU, in the arithmetic of nerf.set_mlp_precision.  The density depends on neither a view direction nor near / far, so none is
-    asked for: the points go through model.hip_sigma as ray origins with a zero direction (ro + 0 * 0 is ro exactly).  Inference
-    only; tensors on a ROCm device.  latent_code=None is allowed exactly for the classes whose forward ignores it."""
+def _point_query(model, points, expr, latent_code, what: str):
+    """The guards nerf.density, nerf.radiance and nerf.vertex_colours share -- a fused model of the NeRFace geometry, ROCm tensors,
+    (N, 3) points, no autograd -- and the conditioning as the kernels take it: (expr (76,), latent (32,)), float32 and contiguous."""
     if not isinstance(model, _FusedNeRFModel) or not model.fused_supported() or (latent_code is None and model.NEEDS_LATENT):
-        raise NotImplementedError("density() is built for the NeRFace geometry and needs expr and latent_code")
+        raise NotImplementedError(f"{what}() is built for the NeRFace geometry and needs expr and latent_code")
     if not (torch.is_tensor(points) and points.is_cuda and torch.is_tensor(expr) and expr.is_cuda):
         raise RuntimeError("nerf (MI355X build): tensors must live on a ROCm device (`device='cuda'`); there is no CPU path in this package")
     if points.dim() != 2 or points.shape[1] != 3:
@@ -112,17 +110,47 @@ def density(model, points, expr, latent_code=None):
     if torch.is_grad_enabled() and (points.requires_grad or latent_code.requires_grad or any(p.requires_grad for p in model.parameters())):
         raise NotImplementedError(f"{type(model).__name__}.forward has no autograd on the MI355X build: train through "
                                   "nerf.run_one_iter_of_nerf(...), or call forward under torch.no_grad()")
+    return ops._c(expr.detach().to(torch.float32)).reshape(-1), ops._c(latent_code.detach().to(torch.float32)).reshape(-1)
+
+
+def density(model, points, expr, latent_code=None):
+    """Raw density (N,) of a fused model at arbitrary points (N, 3) for one expression (and latent code): raw[..., 3], before the
+    ReLU, in the arithmetic of nerf.set_mlp_precision.  The density depends on neither a view direction nor near / far, so none is
+    asked for: the points go through model.hip_sigma as ray origins with a zero direction (ro + 0 * 0 is ro exactly).  Inference
+    only; tensors on a ROCm device.  latent_code=None is allowed exactly for the classes whose forward ignores it."""
+    expr, latent = _point_query(model, points, expr, latent_code, "density")
     n = points.shape[0]
     if n == 0:
         return torch.empty((0,), dtype=torch.float32, device=points.device)
     ro = ops._c(points.detach().to(torch.float32))
-    expr = ops._c(expr.detach().to(torch.float32)).reshape(-1)
-    latent = ops._c(latent_code.detach().to(torch.float32)).reshape(-1)
     ops.bump_pack_epoch()              # as run_one_iter_of_nerf: a weight image never outlives one call (ops.MLPWeights)
     sigma = model.hip_sigma(ro, torch.zeros_like(ro), torch.zeros((n, 1), dtype=torch.float32, device=ro.device), expr, latent, 0.0, 0.0)
     if ops.get_mlp_precision() in ops.F16_MODES:
         ops.check_f16_range(model)
     return sigma.reshape(n)
+
+
+def radiance(model, points, view, expr, latent_code=None, *, near, far):
+    """Raw network output (N, 4) -- colour before the sigmoid, density before the ReLU -- of a fused model at arbitrary points (N, 3)
+    for one expression (and latent code), in the arithmetic of nerf.set_mlp_precision: density's sibling, with the same guards.
+    `view` is (N, 3), or (3,) for all points, and is handed to the network as the view direction; under Quirk Q1 the network's
+    "direction" input is PE4(view z, near, far), so only view[..., 2] reaches it, and near / far are network inputs and have no
+    default.  The points go through model.hip_forward as ray origins with a zero direction, never with live_only: the result is
+    the full forward's output bit for bit.  A family without the arithmetic set refuses by name (NotImplementedError)."""
+    expr, latent = _point_query(model, points, expr, latent_code, "radiance")
+    n = points.shape[0]
+    if not torch.is_tensor(view) or not view.is_cuda or tuple(view.shape) not in ((3,), (n, 3)):
+        raise ValueError(f"radiance: view is a ROCm tensor of shape (3,) or (N, 3) = ({n}, 3), got {tuple(view.shape) if torch.is_tensor(view) else view!r}")
+    if n == 0:
+        return torch.empty((0, 4), dtype=torch.float32, device=points.device)
+    ro = ops._c(points.detach().to(torch.float32))
+    rd_view = ops._c(view.detach().to(torch.float32).expand(n, 3))
+    ops.bump_pack_epoch()              # as density
+    raw, _ = model.hip_forward(ro, torch.zeros_like(ro), torch.zeros((n, 1), dtype=torch.float32, device=ro.device), rd_view, expr, latent,
+                               float(near), float(far), need_grad=False)
+    if ops.get_mlp_precision() in ops.F16_MODES:
+        ops.check_f16_range(model)
+    return raw.reshape(n, 4)
 
 
 class ConditionalBlendshapePaperNeRFModel(_FusedNeRFModel):

@@ -1534,6 +1534,112 @@ def smooth_mesh(vertices: torch.Tensor, faces: torch.Tensor, normals: Optional[t
     return out, faces, out_n, MeshSmoothStats(n_edges, n_boundary, n_boundary if fix_boundary else 0, iterations * (2 if mu != 0.0 else 1))
 
 
+# ---------------------------------------------------------------------------------------- per-vertex radiance of a mesh
+MESH_COLOUR_MAX_SAMPLES = 64                     # nfk::MAX_SAMPLES of csrc/nf_mesh_colour.hip
+
+
+class MeshColours(NamedTuple):
+    colours: torch.Tensor                        # (V, 3) float32 in [0, 1]
+    opacity: torch.Tensor                        # (V,) float32: what the shell through the vertex absorbs; below min_opacity the colour is the middle sample's
+
+
+def _check_colour_args(samples, depth, pose, view_z, what: str):
+    """What the colour pass can refuse without a device; returns (samples, depth as float32, view_z as float32 or None)."""
+    try:
+        whole = not isinstance(samples, bool) and int(samples) == samples and 1 <= int(samples) <= MESH_COLOUR_MAX_SAMPLES
+    except (TypeError, ValueError, OverflowError):
+        whole = False
+    if not whole:
+        raise ValueError(f"{what}: samples is a whole number in [1, {MESH_COLOUR_MAX_SAMPLES}], got {samples!r}")
+    try:
+        depth32 = float(np.float32(depth))
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: depth is a number, got {depth!r}")
+    if not depth32 >= 0.0:                                                          # a NaN fails
+        raise ValueError(f"{what}: depth is the half-thickness of the shell, at least 0, got {depth!r}")
+    if (pose is None) == (view_z is None):
+        raise ValueError(f"{what}: exactly one of pose (a camera-to-world (3, 4) or (4, 4) tensor) and view_z (a number) is given")
+    if pose is not None and (not torch.is_tensor(pose) or pose.dtype != torch.float32 or tuple(pose.shape) not in ((3, 4), (4, 4))):
+        raise ValueError(f"{what}: pose is a float32 tensor of shape (3, 4) or (4, 4)")
+    return int(samples), depth32, None if view_z is None else float(np.float32(view_z))
+
+
+def mesh_colour_step(depth, samples: int) -> float:
+    """The spacing of the samples of mesh_colour_rays, as the kernel forms it in float32: 2 * (depth / samples)."""
+    return float(np.float32(2.0) * (np.float32(depth) / np.float32(samples)))
+
+
+def mesh_colour_rays(vertices: torch.Tensor, normals: torch.Tensor, *, samples: int, depth: float, pose: Optional[torch.Tensor] = None, view_z=None):
+    """The short ray through the surface at every vertex of a mesh on a ROCm device (DESIGN.md "Mesh colours"), in the layout
+    model.hip_forward takes with the vertices as origins: (rd (V, 3), rd_view (V, 3), z (V, samples)).  rd = -normals (the normals
+    point towards lower density); z[k] = float(2 k - samples + 1) * (depth / samples), from outside to inside, the middle sample of
+    an odd count on the vertex; rd_view is the direction the camera `pose` (camera-to-world [R | o]) would have fed the network
+    for the pixel that sees the vertex, (v - o) / d with d the vertex's distance along the camera's axis -- the central ray
+    -R[:, 2] for a vertex that is not in front of the camera -- or (0, 0, view_z) for every vertex.  Every float32 operation
+    rounded on its own (tests/mesh_colour_ref.py gives the same bits).  No host read."""
+    _check_vertices(vertices, "mesh_colour_rays")
+    _check_normals(normals, vertices, "mesh_colour_rays")
+    if normals is None:
+        raise ValueError("mesh_colour_rays: normals must be a float32 tensor of the vertices' shape")
+    samples, depth, view_z = _check_colour_args(samples, depth, pose, view_z, "mesh_colour_rays")
+    dev = _require_same_device("mesh_colour_rays", vertices, normals, pose)
+    n_vertices = int(vertices.shape[0])
+    vertices, normals = vertices.detach().contiguous(), normals.detach().contiguous()
+    pose = None if pose is None else pose.detach().contiguous()
+    rd, rd_view = torch.empty_like(vertices), torch.empty_like(vertices)
+    z = torch.empty((n_vertices, samples), dtype=torch.float32, device=dev)
+    lib = H.lib()
+    with torch.cuda.device(dev):
+        H.check(lib.nf_mesh_colour_rays(H.ptr(vertices), H.ptr(normals), n_vertices, H.ptr(pose), 4, view_z or 0.0, samples, depth, H.ptr(rd),
+                                        H.ptr(rd_view), H.ptr(z), H.stream_ptr(dev)), "nf_mesh_colour_rays")
+    return rd, rd_view, z
+
+
+def mesh_colour_integrate(raw: torch.Tensor, step: float, min_opacity: float = 1e-3) -> MeshColours:
+    """The composite of the network's output raw (V, K, 4) along the rays of mesh_colour_rays, samples `step` apart: sigma =
+    relu(raw[..., 3]), alpha = 1 - exp(-sigma * step), w_k = alpha_k * prod_{j<k}(1 - alpha_j), opacity = sum w, colours = sum w *
+    sigmoid(raw[..., :3]) / opacity where opacity >= min_opacity, else the sigmoid of sample K // 2 (the vertex itself for an odd K).
+    No background sample and nothing added at the far end, unlike the camera-ray integrator.  Sums in ascending k, no float
+    atomics: the same bits from run to run.  A min_opacity of 0 divides 0 by 0 where nothing absorbs.  No host read."""
+    if not torch.is_tensor(raw) or raw.dtype != torch.float32 or raw.dim() != 3 or raw.shape[2] != 4 or not 1 <= raw.shape[1] <= MESH_COLOUR_MAX_SAMPLES:
+        raise ValueError(f"mesh_colour_integrate: raw is a float32 tensor of shape (V, K, 4) with K in [1, {MESH_COLOUR_MAX_SAMPLES}]")
+    step, min_opacity = float(np.float32(step)), float(np.float32(min_opacity))
+    if not step >= 0.0 or min_opacity != min_opacity:
+        raise ValueError(f"mesh_colour_integrate: step is at least 0 and min_opacity a number, got {step!r} and {min_opacity!r}")
+    dev = _require_same_device("mesh_colour_integrate", raw)
+    raw = raw.detach().contiguous()
+    n_vertices, samples = int(raw.shape[0]), int(raw.shape[1])
+    colours = torch.empty((n_vertices, 3), dtype=torch.float32, device=dev)
+    opacity = torch.empty((n_vertices,), dtype=torch.float32, device=dev)
+    lib = H.lib()
+    with torch.cuda.device(dev):
+        H.check(lib.nf_mesh_colour_integrate(H.ptr(raw), n_vertices, samples, step, min_opacity, H.ptr(colours), H.ptr(opacity), H.stream_ptr(dev)),
+                "nf_mesh_colour_integrate")
+    return MeshColours(colours, opacity)
+
+
+def vertex_colours(forward, vertices: torch.Tensor, normals: torch.Tensor, *, samples: int = 8, depth: float, pose: Optional[torch.Tensor] = None,
+                   view_z=None, min_opacity: float = 1e-3, chunk_points: int = 1 << 22) -> MeshColours:
+    """The colour of every vertex of a mesh under the radiance field `forward(ro, rd, z, rd_view) -> raw (n, samples, 4)`:
+    mesh_colour_rays, the field, mesh_colour_integrate, in slabs of max(1, chunk_points // samples) whole vertices.  Every vertex
+    is on its own, so the result does not depend on chunk_points.  No vertices: empty tensors, and nothing is launched."""
+    _check_vertices(vertices, "vertex_colours")
+    _check_normals(normals, vertices, "vertex_colours")
+    samples, depth, _ = _check_colour_args(samples, depth, pose, view_z, "vertex_colours")
+    dev = _require_same_device("vertex_colours", vertices, normals, pose)
+    n_vertices = int(vertices.shape[0])
+    colours = torch.empty((n_vertices, 3), dtype=torch.float32, device=dev)
+    opacity = torch.empty((n_vertices,), dtype=torch.float32, device=dev)
+    slab = max(1, int(chunk_points) // samples)
+    step = mesh_colour_step(depth, samples)
+    vertices, normals = vertices.detach().contiguous(), normals.detach().contiguous()
+    for v0 in range(0, n_vertices, slab):
+        ro = vertices[v0:v0 + slab]
+        rd, rd_view, z = mesh_colour_rays(ro, normals[v0:v0 + slab], samples=samples, depth=depth, pose=pose, view_z=view_z)
+        colours[v0:v0 + slab], opacity[v0:v0 + slab] = mesh_colour_integrate(forward(ro, rd, z, rd_view), step, min_opacity)
+    return MeshColours(colours, opacity)
+
+
 # ---------------------------------------------------------------------------------------- sparse evaluation of a dense grid
 class SparseGridStats(NamedTuple):
     bricks: int                                  # bricks of the grid

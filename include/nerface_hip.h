@@ -773,6 +773,26 @@ int nf_mesh_smooth_run(const float* vertices, int64_t n_vertices, const int* row
 int nf_mesh_smooth_normals(const float* vertices, const int* faces, int64_t n_vertices, int64_t n_faces, void* workspace,
                            size_t workspace_bytes, float* normals, nf_stream_t stream);
 
+/* ---- per-vertex radiance of a mesh (ABI 5 still: these only add) ---------------------------------------------------------------------
+ * DESIGN.md "Mesh colours" is the specification.  vertices, normals: f32 [V][3], 0 <= V < 2^31, the normals towards lower density;
+ * 1 <= n_samples = K <= 64.
+ *   nf_mesh_colour_rays       the short ray through the surface at every vertex, in the layout the forwards take (the vertices are
+ *                             its origins): rd[V][3] = -normals (a sign flip); z[V][K], z[k] = float(2 k - K + 1) * (depth / float(K)),
+ *                             from outside to inside; rd_view[V][3], the direction a camera would have fed the network (only its z
+ *                             reaches it) -- c2w: 12 device floats, R | o, row r at c2w + r * c2w_row_stride (>= 4): t = v - o,
+ *                             d = -((t0 R02 + t1 R12) + t2 R22); d > 0: t / d, else the central ray (-R02, -R12, -R22); c2w == NULL:
+ *                             (0, 0, view_z).  Every operation rounded on its own, in this association.
+ *   nf_mesh_colour_integrate  raw[V][K][4] (16-byte aligned), step = the samples' spacing: sigma = relu(raw[k][3]) (a NaN stays),
+ *                             alpha = 1 - expf(-sigma step), w = alpha * prod_{j<k}(1 - alpha_j), opacity[V] = sum w, colour[V][3] =
+ *                             sum w sigmoid(raw[k][:3]) / opacity where opacity >= min_opacity, else sigmoid(raw[K / 2][:3]); sums in
+ *                             ascending k.  No background sample, nothing added to a density, no scaling by |rd|.
+ * n_vertices == 0 returns 0.  NF_EINVAL before any launch: NULL pointers, K outside [1, 64], depth or step negative or not a number,
+ * min_opacity not a number, a row stride below 4.  Nothing outside the named ranges is written; two calls give the same bits.      */
+int nf_mesh_colour_rays(const float* vertices, const float* normals, int64_t n_vertices, const float* c2w, int64_t c2w_row_stride,
+                        float view_z, int n_samples, float depth, float* rd, float* rd_view, float* z, nf_stream_t stream);
+int nf_mesh_colour_integrate(const float* raw, int64_t n_vertices, int n_samples, float step, float min_opacity, float* colour,
+                             float* opacity, nf_stream_t stream);
+
 /* ---- host-only self-tests (no device needed): consistency of the weight-gradient job tables -- every slab entry written
  * exactly once per slice, tile ids inside their bundle.  0 = consistent, negative = which check failed.                 */
 int nf_selftest_dw_tables_f32(void);
