@@ -33,7 +33,9 @@ SOURCES = ["nf_lib.hip", "nf_rays.hip", "nf_choice.hip", "nf_render.hip", "nf_re
            # Taubin smoothing of a mesh over the CSR table of its vertices' neighbours, and the vertex normals of its faces
            "nf_mesh_smooth.hip",
            # per-vertex radiance of a mesh: the short ray through the surface at every vertex, and the composite along it
-           "nf_mesh_colour.hip"]
+           "nf_mesh_colour.hip",
+           # decimation of a mesh by vertex clustering: two hash sets (cells, welded faces), fixed-point cluster positions
+           "nf_mesh_decimate.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-fvisibility=default",
          "-Wno-unused-result"]
 

@@ -4,7 +4,7 @@ launch/eval_sharded.py picks them), the raw density on a dense grid (nerf.densit
 
     python -m launch.extract_mesh --config cfg.yml --checkpoint ck --frame I --level L --resolution N [Ny Nz] --out mesh.ply \
         [--bounds x0 y0 z0 x1 y1 z1] [--precision f32|f16x3|f16x2|bf16x3] [--coarse] [--brick B [--margin M] [--dilate D]] \
-        [--largest | --min-faces N] [--smooth N [--smooth-lambda L] [--smooth-mu M]] \
+        [--largest | --min-faces N] [--smooth N [--smooth-lambda L] [--smooth-mu M]] [--decimate K] \
         [--colour [--colour-samples K] [--colour-depth D] [--colour-view-z Z]]
 
 Without --bounds the box is the axis-aligned hull of the frame's camera frustum between the config's near and far planes (the
@@ -15,10 +15,14 @@ within --dilate bricks of those.  A feature thinner than a brick that passes bet
 --largest keeps the connected component with the most faces, --min-faces N every component with at least N faces (nerf.filter_mesh,
 on the device): a trained model's floaters are small components of their own.  --smooth N runs N iterations of Taubin's lambda | mu
 smoothing on what is left (nerf.smooth_mesh, on the device; the border a box cuts into the surface stays where it is) and writes
-the normals of the smoothed faces in place of the density gradient's.  --colour writes a colour per vertex of that final mesh
+the normals of the smoothed faces in place of the density gradient's.  --decimate K then clusters the vertices on cells of K grid
+cells from the box's corner (nerf.decimate_mesh, on the device): the vertices of one cell become one, faces that lose a corner go,
+coincident faces are welded; extract fine, clean and smooth, then reduce to the size a viewer takes.  --colour writes a colour per
+vertex of that final mesh
 (nerf.vertex_colours, from the same network as the density): K samples (default 8) on a ray along the normal through a shell of
-half-thickness D round the surface (default: the diagonal of a grid cell), composited and normalised, seen from the frame's camera
-(its pose and the config's near / far), or with the view direction (0, 0, Z) under --colour-view-z.
+half-thickness D round the surface (default: the diagonal of a grid cell, or of a decimation cell under --decimate K with K > 1),
+composited and normalised, seen from the frame's camera (its pose and the config's near / far), or with the view direction
+(0, 0, Z) under --colour-view-z.
 """
 from __future__ import annotations
 
@@ -69,9 +73,12 @@ def _main(argv=None):
     ap.add_argument("--smooth", type=int, default=0, metavar="N", help="iterations of Taubin smoothing after the component filter (default: none)")
     ap.add_argument("--smooth-lambda", type=float, default=0.5, metavar="L", help="with --smooth: the shrinking factor, 0 < L <= 1")
     ap.add_argument("--smooth-mu", type=float, default=-0.53, metavar="M", help="with --smooth: the inflating factor, -1 <= M <= 0 (0: plain Laplacian smoothing)")
+    ap.add_argument("--decimate", type=float, default=None, metavar="K", help="cluster the vertices on cells of K grid cells, K > 0, after --smooth and before "
+                    "--colour (default: no decimation)")
     ap.add_argument("--colour", action="store_true", help="write a colour per vertex of the final mesh, from the same network as the density")
     ap.add_argument("--colour-samples", type=int, default=8, metavar="K", help="with --colour: samples on the ray through every vertex, 1 .. 64")
-    ap.add_argument("--colour-depth", type=float, default=None, metavar="D", help="with --colour: half-thickness of the sampled shell (default: a grid cell's diagonal)")
+    ap.add_argument("--colour-depth", type=float, default=None, metavar="D", help="with --colour: half-thickness of the sampled shell (default: a grid cell's diagonal; with "
+                    "--decimate K > 1 a decimation cell's, which is how far the true surface can lie from a clustered vertex)")
     ap.add_argument("--colour-view-z", type=float, default=None, metavar="Z", help="with --colour: the view direction (0, 0, Z) in place of the frame's camera")
     args = ap.parse_args(argv)
     if len(args.resolution) not in (1, 3):
@@ -84,6 +91,8 @@ def _main(argv=None):
         ap.error("--min-faces takes at least 1")
     if args.smooth < 0 or not 0.0 < args.smooth_lambda <= 1.0 or not -1.0 <= args.smooth_mu <= 0.0:
         ap.error("--smooth takes at least 0 iterations, --smooth-lambda a factor in (0, 1] and --smooth-mu one in [-1, 0]")
+    if args.decimate is not None and not 0.0 < args.decimate < float("inf"):
+        ap.error("--decimate takes a number of grid cells above 0")
     if not 1 <= args.colour_samples <= ops.MESH_COLOUR_MAX_SAMPLES or (args.colour_depth is not None and not args.colour_depth >= 0.0):
         ap.error(f"--colour-samples takes 1 to {ops.MESH_COLOUR_MAX_SAMPLES} samples and --colour-depth at least 0")
     if not torch.cuda.is_available():
@@ -135,11 +144,17 @@ def _main(argv=None):
         mesh = nerf.Mesh(*kept)
     smooth = None
     if args.smooth:
+        n_smoothed = int(mesh.vertices.shape[0])
         *smoothed, smooth = ops.smooth_mesh(*mesh, iterations=args.smooth, lam=args.smooth_lambda, mu=args.smooth_mu)
         mesh = nerf.Mesh(*smoothed)
+    decimate = None
+    if args.decimate is not None:
+        cell, origin = nerf.mesh.decimation_lattice(lo, hi, res, args.decimate)
+        *lighter, _, decimate = ops.decimate_mesh(*mesh, cell=cell, origin=origin)
+        mesh = nerf.Mesh(*lighter)
     colour = None
     if args.colour:
-        cell = [(float(h) - float(l)) / (int(n) - 1) for l, h, n in zip(lo, hi, res)]
+        cell = [max(args.decimate or 1.0, 1.0) * (float(h) - float(l)) / (int(n) - 1) for l, h, n in zip(lo, hi, res)]
         depth = args.colour_depth if args.colour_depth is not None else float(np.sqrt(sum(c * c for c in cell)))
         view = dict(view_z=args.colour_view_z) if args.colour_view_z is not None else dict(pose=poses[args.frame, :3, :4].float().to(dev))
         min_opacity = 1e-3
@@ -166,7 +181,12 @@ def _main(argv=None):
     if smooth is not None:
         stats["smooth"] = smooth._asdict()
         print(f"smoothed: {args.smooth} iterations (lambda {args.smooth_lambda}, mu {args.smooth_mu}) in {smooth.passes} passes over {smooth.edges // 2} edges; "
-              f"{smooth.pinned_vertices} boundary vertices of {stats['vertices']} stay where they are")
+              f"{smooth.pinned_vertices} boundary vertices of {n_smoothed} stay where they are")
+    if decimate is not None:
+        stats["decimate"] = decimate._asdict()
+        print(f"decimated: cells of {args.decimate:g} grid cells; vertices {decimate.kept_vertices} of {decimate.vertices}, faces {decimate.kept_faces} of "
+              f"{decimate.faces} ({decimate.degenerate_faces} degenerate, {decimate.coincident_faces} coincident); the largest cluster holds "
+              f"{decimate.largest_cluster} vertices")
     if colour is not None:
         stats["colour"] = colour
         print(f"coloured: {colour['vertices']} vertices, {colour['samples']} samples over a shell of half-thickness {colour['depth']:.6g}; "

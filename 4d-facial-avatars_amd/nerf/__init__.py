@@ -27,6 +27,7 @@ from .models import radiance  # MI355X extension: the raw (N, 4) output of a fus
 from .mesh import density_grid_sparse  # MI355X extension: that grid evaluated only in the bricks near one level's surface (ops.sparse_grid)
 from .mesh import Mesh, density_grid, extract_mesh, write_mesh  # MI355X extension: a model's density on a grid and the triangle mesh of one level (ops.isosurface)
 from .mesh import smooth_mesh, vertex_normals  # MI355X extension: Taubin smoothing of a mesh and the unit normals of its faces (ops.smooth_mesh, ops.vertex_normals)
+from .mesh import decimate_mesh  # MI355X extension: a lighter mesh by vertex clustering on a lattice, coincident faces welded (ops.decimate_mesh)
 from .mesh import filter_mesh, mesh_components  # MI355X extension: a mesh's connected components; its largest, or those of at least N faces (ops.filter_mesh)
 from .mesh import MeshColours, vertex_colours  # MI355X extension: per-vertex radiance of a mesh (ops.mesh_colour_rays, ops.mesh_colour_integrate)
 from .train_graph import GraphedTrainer  # MI355X extension: the training iteration captured once in a HIP graph and replayed (single rank)

@@ -228,6 +228,10 @@ _PROTOTYPES["nf_mesh_smooth_run"] = (C.c_int, [_P, _L, _P, _P, _P, _I, _F, _F, _
 _PROTOTYPES["nf_mesh_smooth_normals"] = (C.c_int, [_P, _P, _L, _L, _P, _Z, _P, _P])
 _PROTOTYPES["nf_mesh_colour_rays"] = (C.c_int, [_P, _P, _L, _P, _L, _F, _I, _F, _P, _P, _P, _P])
 _PROTOTYPES["nf_mesh_colour_integrate"] = (C.c_int, [_P, _L, _I, _F, _F, _P, _P, _P])
+# decimation of an indexed mesh by vertex clustering: the eight counts on the device, then the kept vertices, faces and the vertex map
+_PROTOTYPES["nf_mesh_decimate_workspace_bytes"] = (_Z, [_L, _L])
+_PROTOTYPES["nf_mesh_decimate_count"] = (C.c_int, [_P, _P, _L, _L, _P, _P, _P, _Z, _P, _P])
+_PROTOTYPES["nf_mesh_decimate_emit"] = (C.c_int, [_P, _P, _L, _L, _P, _P, _P, _Z, _P, _L, _P, _L, _P, _P])
 for _prefix in ("nf_lcode", "nf_bshape", "nf_cbshape"):          # measurement hook (tools/time_blendshape.py)
     _PROTOTYPES[f"{_prefix}_mlp_bwd_stage_ms"] = (C.c_int, [_P, _P, _I, _P, _P, _P, _L, _I, _P, _Z, _P, _P, _P])
 # entry points that later ABI revisions add; absent symbols only fail when called

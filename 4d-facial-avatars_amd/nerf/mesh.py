@@ -7,6 +7,7 @@
     filter_mesh(mesh, largest= | min_faces=)                               -> the Mesh of the largest component, or of those of >= N faces
     smooth_mesh(mesh, iterations=, lam=, mu=, fix_boundary=)               -> the Mesh after Taubin smoothing, its normals recomputed
     vertex_normals(mesh)                                                   -> (V, 3) unit normals from the faces
+    decimate_mesh(mesh, cell=, origin=)                                    -> the lighter Mesh of vertex clustering on a lattice of `cell`
     vertex_colours(model, mesh, expr, latent_code, near=, far=, pose= | view_z=, samples=, depth=)
                                                                            -> MeshColours(colours (V, 3) in [0, 1], opacity (V,))
     write_mesh(path, mesh, colours=None)                                   -> .off / .obj / .ply (binary little-endian), host code
@@ -14,7 +15,7 @@
 The density comes from the density-only kernels (nerf.density), the surface from ops.isosurface (csrc/nf_isosurface.hip), the choice
 of the points near the surface from ops.sparse_grid (csrc/nf_sparse_grid.hip), the components from ops.mesh_components and
 ops.filter_mesh (csrc/nf_mesh_components.hip), smoothing and face normals from ops.smooth_mesh and ops.vertex_normals
-(csrc/nf_mesh_smooth.hip).  The colours come from the model's full forward (the network nerf.radiance queries) on a short ray through
+(csrc/nf_mesh_smooth.hip), decimation from ops.decimate_mesh (csrc/nf_mesh_decimate.hip).  The colours come from the model's full forward (the network nerf.radiance queries) on a short ray through
 the surface at every vertex, along the normal, composited and normalised by ops.mesh_colour_rays and ops.mesh_colour_integrate
 (csrc/nf_mesh_colour.hip; DESIGN.md "Mesh colours"); write_mesh stores them per vertex in each of its three formats.
 """
@@ -122,9 +123,38 @@ def vertex_normals(mesh) -> torch.Tensor:
     return ops.vertex_normals(vertices, faces)
 
 
+def decimate_mesh(mesh, *, cell, origin=(0.0, 0.0, 0.0)) -> Mesh:
+    """The lighter Mesh (or (vertices, faces[, normals]) tuple) of vertex clustering (ops.decimate_mesh): the vertices inside one cell
+    of the lattice origin + cell * (i, j, k) -- `cell` one number or three, in the mesh's units -- become one vertex at their mean,
+    faces that lose a corner that way go, faces that end on one vertex set are welded into one; order and winding of what is kept
+    stay.  Normals, if the mesh has them, become vertex_normals of the result.  ops.decimate_mesh also returns the map from old to
+    new vertices and the statistics."""
+    vertices, faces, normals = _mesh_fields(mesh, "decimate_mesh")
+    return Mesh(*ops.decimate_mesh(vertices, faces, normals, cell=cell, origin=origin)[:3])
+
+
+def _decimate_cells(decimate, what: str):
+    """None, or K > 0 as a float: the edge of a decimation cell in grid cells."""
+    if decimate is None:
+        return None
+    try:
+        k = None if isinstance(decimate, (bool, str)) else float(decimate)
+    except (TypeError, ValueError):
+        k = None
+    if k is None or not (0.0 < k < float("inf")):
+        raise ValueError(f"{what}: decimate is None or a number of grid cells > 0, got {decimate!r}")
+    return k
+
+
+def decimation_lattice(lo, hi, resolution, k):
+    """(cell, origin) of the lattice extract_mesh(decimate=k) clusters on: cells of k grid cells, k * (hi - lo) / (n - 1) per axis,
+    from the box's corner `lo`."""
+    return [float(k) * (float(h) - float(l)) / (int(n) - 1) for l, h, n in zip(lo, hi, _resolution(resolution))], [float(x) for x in lo]
+
+
 def extract_mesh(model, expr, latent_code=None, *, lo, hi, resolution, level, normals: bool = True, chunk_points: int = 1 << 22, brick=None,
                  margin: float = 0.0, dilate: int = 1, largest: bool = False, min_faces=None, smooth: int = 0, smooth_lam: float = 0.5,
-                 smooth_mu: float = -0.53) -> Mesh:
+                 smooth_mu: float = -0.53, decimate=None) -> Mesh:
     """The surface raw density == level of a fused model inside the box [lo, hi] for one expression (and latent code): density_grid,
     then ops.isosurface.  `level` is in raw-density units (before the ReLU of the volume renderer) and has no default: what counts
     as surface depends on the scene's scale and on how the model was trained.  With `brick` (cells per brick, e.g. 8) the grid is
@@ -133,7 +163,9 @@ def extract_mesh(model, expr, latent_code=None, *, lo, hi, resolution, level, no
     need dilate >= 1.  With largest=True or min_faces=N the mesh is filter_mesh's: its largest component, or those of at least N
     faces; with neither (the default) nothing more is launched.  With smooth=N the result is smooth_mesh's after N iterations with
     smooth_lam and smooth_mu, run after the component filter, so that floaters are not smoothed; at the default 0 nothing more is
-    launched."""
+    launched.  With decimate=K > 0 the result is decimate_mesh's on cells of K grid cells (cell = K h per axis, origin = lo), run
+    after the filter and the smoothing: extract fine, then reduce; at the default None nothing more is launched."""
+    decimate = _decimate_cells(decimate, "extract_mesh")
     try:
         whole = not isinstance(smooth, bool) and int(smooth) == smooth and int(smooth) >= 0
     except (TypeError, ValueError, OverflowError):
@@ -155,7 +187,12 @@ def extract_mesh(model, expr, latent_code=None, *, lo, hi, resolution, level, no
     mesh = Mesh(*ops.isosurface(grid, float(level), lo, hi, normals=normals))
     if clean:
         mesh = filter_mesh(mesh, largest=largest, min_faces=min_faces)
-    return smooth_mesh(mesh, iterations=int(smooth), lam=smooth_lam, mu=smooth_mu) if int(smooth) else mesh
+    if int(smooth):
+        mesh = smooth_mesh(mesh, iterations=int(smooth), lam=smooth_lam, mu=smooth_mu)
+    if decimate is not None:
+        cell, origin = decimation_lattice(lo, hi, resolution, decimate)
+        mesh = decimate_mesh(mesh, cell=cell, origin=origin)
+    return mesh
 
 
 def vertex_colours(model, mesh, expr, latent_code=None, *, near, far, pose=None, view_z=None, samples: int = 8, depth, min_opacity: float = 1e-3,

@@ -1534,8 +1534,91 @@ def smooth_mesh(vertices: torch.Tensor, faces: torch.Tensor, normals: Optional[t
     return out, faces, out_n, MeshSmoothStats(n_edges, n_boundary, n_boundary if fix_boundary else 0, iterations * (2 if mu != 0.0 else 1))
 
 
+# ---------------------------------------------------------------------------------------- decimation of a mesh by vertex clustering
+MESH_DECIMATE_MAX = 2 ** 30                      # nfd::MAX_ELEMENTS of csrc/nf_mesh_decimate.hip: V and F, so that ids and table slots fit 31 bits
+
+
+class MeshDecimateStats(NamedTuple):
+    vertices: int
+    kept_vertices: int
+    faces: int
+    kept_faces: int
+    degenerate_faces: int                        # valid faces with two corners in one cluster
+    coincident_faces: int                        # non-degenerate valid faces not kept: the others of a vertex set, both sides of a collapsed sheet
+    invalid_faces: int                           # faces with an index outside [0, V)
+    unclustered_vertices: int                    # NaN, infinite or past the 2^21 cells per axis: each a cluster of its own
+    largest_cluster: int                         # members of the largest cluster
+
+
+def _check_decimate_args(vertices, faces, normals, cell, origin, what: str):
+    """Everything decimate_mesh can refuse without a device; returns (V, F, cell, origin), the last two as three float32 each."""
+    _check_vertices(vertices, what)
+    n_vertices, n_faces = _check_faces(faces, vertices.shape[0], what)
+    _check_normals(normals, vertices, what)
+    if n_vertices > MESH_DECIMATE_MAX or n_faces > MESH_DECIMATE_MAX:
+        raise ValueError(f"{what}: V and F lie in [0, 2^30] (ids and table slots fit 31 bits), got V = {n_vertices} and F = {n_faces}")
+    try:
+        if isinstance(cell, (bool, str)) or isinstance(origin, (bool, str)):
+            raise TypeError
+        cell32, origin32 = np.asarray(cell, dtype=np.float32).reshape(-1), np.asarray(origin, dtype=np.float32).reshape(-1)
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: cell is one number or three and origin three numbers, got {cell!r} and {origin!r}")
+    if cell32.size == 1:
+        cell32 = np.repeat(cell32, 3)
+    if cell32.size != 3 or origin32.size != 3:
+        raise ValueError(f"{what}: cell is one number or three and origin three numbers, got {cell!r} and {origin!r}")
+    if not bool(np.all(np.isfinite(cell32) & (cell32 > 0))) or not bool(np.all(np.isfinite(origin32))):
+        raise ValueError(f"{what}: every cell size is finite and > 0 and the origin finite (in float32), got cell = {cell!r} and origin = {origin!r}")
+    return n_vertices, n_faces, cell32, origin32
+
+
+def decimate_mesh(vertices: torch.Tensor, faces: torch.Tensor, normals: Optional[torch.Tensor] = None, *, cell, origin=(0.0, 0.0, 0.0)):
+    """A lighter mesh by vertex clustering on a ROCm device (DESIGN.md "Mesh decimation"): the vertices that fall into one cell of the
+    lattice origin + cell * (i, j, k) -- `cell` one number or three, in the mesh's units -- become one vertex at their mean (taken
+    in the cell's 2^30 fixed point, so it does not depend on the order of the sum; a vertex alone in its cell keeps its floats bit
+    for bit).  A face becomes the triple of its corners' clusters; it goes if two corners share a cluster, and of the faces that end
+    on one vertex set the one of the majority orientation with the smallest id stays, or none where both orientations are as many
+    (the two sides of a collapsed sheet cancel).  Kept faces keep their order and winding; clusters no kept face uses are dropped,
+    which includes vertices no face used.  A NaN or infinite vertex, or one past 2^20 cells from the origin, is a cluster of its
+    own; a face with an index outside [0, V) takes no part.  A closed mesh usually stays closed and keeps its Euler characteristic;
+    vertex clustering never guarantees it.
+
+    Returns (vertices, faces, normals or None, vertex_map, MeshDecimateStats): vertex_map (V,) int32 holds the new id of every old
+    vertex's cluster, -1 for a dropped one -- what carries a caller's own attributes across; normals, if given, are replaced by
+    vertex_normals of the result (nothing is averaged).  An empty result is made of (0, 3) tensors.  Integer atomics only
+    (csrc/nf_mesh_decimate.hip): the same bits from run to run.  Exactly one host read here (the counts that size the outputs)."""
+    n_vertices, n_faces, cell32, origin32 = _check_decimate_args(vertices, faces, normals, cell, origin, "decimate_mesh")
+    dev = _require_same_device("decimate_mesh", vertices, faces, normals)
+    vertices_in, faces_in = vertices.detach().contiguous(), faces.detach().contiguous()
+    lib = H.lib()
+    ws, ws_bytes = _workspace(lib, "nf_mesh_decimate_workspace_bytes", (n_vertices, n_faces), dev,
+                              f"decimate_mesh: {n_vertices} vertices and {n_faces} faces are past the plan of csrc/nf_mesh_decimate.hip (both at most 2^30)")
+    c_origin, c_cell = (C.c_float * 3)(*origin32.tolist()), (C.c_float * 3)(*cell32.tolist())
+    counts = torch.empty(8, dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        stream = H.stream_ptr(dev)
+        H.check(lib.nf_mesh_decimate_count(H.ptr(vertices_in), H.ptr(faces_in), n_vertices, n_faces, C.addressof(c_origin), C.addressof(c_cell), H.ptr(ws),
+                                           ws_bytes, H.ptr(counts), stream), "nf_mesh_decimate_count")
+        kept_v, kept_f, degenerate, coincident, invalid, unclustered, largest, overflow = counts.tolist()       # the one host read
+        if overflow:
+            raise RuntimeError("decimate_mesh: a hash set of csrc/nf_mesh_decimate.hip ran full, which its load of at most 0.5 excludes: nothing is returned")
+        if normals is not None:
+            _check_smooth_sizes(kept_v, kept_f, "decimate_mesh (the normals of the result)")
+        out_v = torch.empty((kept_v, 3), dtype=torch.float32, device=dev)
+        out_f = torch.empty((kept_f, 3), dtype=torch.int32, device=dev)
+        vertex_map = torch.empty(n_vertices, dtype=torch.int32, device=dev)
+        if n_vertices:
+            H.check(lib.nf_mesh_decimate_emit(H.ptr(vertices_in), H.ptr(faces_in), n_vertices, n_faces, C.addressof(c_origin), C.addressof(c_cell),
+                                              H.ptr(ws), ws_bytes, H.ptr(out_v), kept_v, H.ptr(out_f), kept_f, H.ptr(vertex_map), stream),
+                    "nf_mesh_decimate_emit")
+        out_n = None
+        if normals is not None:
+            out_n = _vertex_normals(lib, out_v, out_f, kept_v, kept_f, dev) if kept_v else torch.empty((0, 3), dtype=torch.float32, device=dev)
+    return out_v, out_f, out_n, vertex_map, MeshDecimateStats(n_vertices, kept_v, n_faces, kept_f, degenerate, coincident, invalid, unclustered, largest)
+
+
 # ---------------------------------------------------------------------------------------- per-vertex radiance of a mesh
-MESH_COLOUR_MAX_SAMPLES = 64                     # nfk::MAX_SAMPLES of csrc/nf_mesh_colour.hip
+MESH_COLOUR_MAX_SAMPLES = 64                    # nfk::MAX_SAMPLES of csrc/nf_mesh_colour.hip
 
 
 class MeshColours(NamedTuple):

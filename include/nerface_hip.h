@@ -793,6 +793,34 @@ int nf_mesh_colour_rays(const float* vertices, const float* normals, int64_t n_v
 int nf_mesh_colour_integrate(const float* raw, int64_t n_vertices, int n_samples, float step, float min_opacity, float* colour,
                              float* opacity, nf_stream_t stream);
 
+/* ---- decimation of an indexed mesh by vertex clustering, with welded faces (ABI 5 still: these only add) -----------------------------
+ * DESIGN.md "Mesh decimation" is the specification.  vertices: f32 [V][3], faces: int32 [F][3], 0 <= V, F <= 2^30; origin, cell: HOST
+ * float[3], the cell finite and > 0.  Per axis t = (p - o) / c in float32, i = floor(t); a vertex is clustered iff all three t are
+ * finite and -2^20 <= i < 2^20, and the clustered vertices of one cell are one cluster, every other vertex a cluster of its own; the
+ * representative of a cluster is its smallest vertex id.  A face with an index outside [0, V) takes no part; a valid face becomes the
+ * triple of its representatives, dropped as degenerate iff two are equal; of the faces with one vertex set none is kept if as many
+ * are even as odd permutations of the ascending triple, else the one of the majority orientation with the smallest face id.
+ * workspace: nf_mesh_decimate_workspace_bytes(V, F) bytes, 8-byte aligned, any content; 0 = a size that is not served.
+ *   nf_mesh_decimate_count    clustering, the face set, the used marks and both scans; counts_dev[8] (int64, on the device) = V', F',
+ *                             degenerate faces, coincident faces (non-degenerate valid faces not kept), invalid faces, unclustered
+ *                             vertices, the largest cluster, the overflow flag (a probe of a hash set visited every slot: never at
+ *                             the load of at most 0.5 the plan keeps; the other counts mean nothing then).
+ *   nf_mesh_decimate_emit     with the same mesh, origin and cell and the workspace as count left it: out_vertices [V'][3] = the used
+ *                             representatives in ascending order -- a cluster of one member its floats bit for bit, a larger one the
+ *                             mean of its members in the cell's 2^30 fixed point, order-independent; out_faces [F'][3] = the kept faces
+ *                             in their order and winding, renumbered; vertex_map[V] = the new id of v's representative, -1 for a
+ *                             cluster no kept face uses.  n_out_vertices / n_out_faces must be V' and F' as count found them: this
+ *                             call reads those two words back (it waits for the stream) and, if they differ, writes nothing.
+ * NF_EINVAL before any launch: NULL pointers where the size is not 0, an unserved size, workspace_bytes too small, a cell that is
+ * NaN, infinite or <= 0, an origin that is NaN or infinite, n_out_vertices / n_out_faces other than V' / F'.  Integer atomics only:
+ * two calls give the same bits.                                                                                                   */
+size_t nf_mesh_decimate_workspace_bytes(int64_t n_vertices, int64_t n_faces);
+int nf_mesh_decimate_count(const float* vertices, const int* faces, int64_t n_vertices, int64_t n_faces, const float* origin,
+                           const float* cell, void* workspace, size_t workspace_bytes, int64_t* counts_dev, nf_stream_t stream);
+int nf_mesh_decimate_emit(const float* vertices, const int* faces, int64_t n_vertices, int64_t n_faces, const float* origin,
+                          const float* cell, void* workspace, size_t workspace_bytes, float* out_vertices, int64_t n_out_vertices,
+                          int* out_faces, int64_t n_out_faces, int* vertex_map, nf_stream_t stream);
+
 /* ---- host-only self-tests (no device needed): consistency of the weight-gradient job tables -- every slab entry written
  * exactly once per slice, tile ids inside their bundle.  0 = consistent, negative = which check failed.                 */
 int nf_selftest_dw_tables_f32(void);
